@@ -10,6 +10,17 @@ Every timed step is a full training step: forward, softmax-xent loss, backward (
 conv/BN/pool kernels), bucketed RCCL all-reduce of all 25.6 M gradients (N > 1), and the fused
 momentum-SGD + weight-decay update of every parameter.  Data: synthetic ImageNet-shaped batch
 (random bf16 images, random labels) resident in HBM; weights random-init (no checkpoints/datasets).
+
+A plain run sets up, warms up, times the K steps and prints the line.  ``--dump-outputs DIR`` also writes
+what the last timed step computed (loss, gradients, updated parameters; seeded inputs, so two builds can be
+compared array for array).  The default step sums BN statistics and split-K weight gradients with fp32
+atomics, and the random-init network amplifies that order noise: after 25 steps two runs of ONE build agree
+to ~1 % in the loss only, the gradients not at all.  A run with ``--dump-outputs`` therefore switches the
+kernels to their fixed summation order (ops._lib.set_deterministic, as DTM_DETERMINISTIC=1 does): its arrays
+are bit-identical from run to run, its steps ~5 % slower (17.5 vs 16.7 ms), and its result line says so
+(``config.deterministic``).  A run without the option is the headline figure at full speed.
+``--full`` adds the measurements the headline figure does not need (the N > 1
+per-phase and per-bucket all-reduce times, ``config.phases_ms``, taken in 3 extra steps).
 """
 import argparse
 import json
@@ -62,6 +73,14 @@ def main():
                     help="pin the RCCL channel count (NCCL_MIN/MAX_NCHANNELS); 0 = RCCL's own choice")
     ap.add_argument("--device", default="cuda", choices=("cuda", "cpu"),
                     help="cpu: the plumbing config (LeNet over gloo, no GPU; BASELINE.json config 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the per-phase HIP-event sections and "
+                    "per-bucket all-reduce times of 3 extra steps after the timed ones (N > 1; config.phases_ms)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (float32): its "
+                    "loss, and fixed seeded samples of the reduced gradients and of the updated parameters; turns on "
+                    "the kernels' fixed-order reductions, so the arrays are bit-identical run to run (steps ~5 %% "
+                    "slower)")
     args = ap.parse_args()
 
     env_world = os.environ.get("WORLD_SIZE")
@@ -103,6 +122,14 @@ def main():
     from distributed_tensorflow_models_amd.engine import TrainStep
     from distributed_tensorflow_models_amd.models import nets_factory
 
+    deterministic = None  # (CPU: the reference ops have no atomics)
+    if not cpu:
+        from distributed_tensorflow_models_amd.ops import _lib
+        if args.dump_outputs:
+            # outputs that two runs (and two builds) can be compared by: every reduction in a fixed order,
+            # set before the first kernel runs
+            _lib.set_deterministic(True)
+        deterministic = bool(_lib.lib().dtm_get_deterministic())
     if args.graph < 0:
         # measured on one MI355X (profiles/ab/r2_ab_graph_bench.log): LeNet 396k -> 875k img/s with the
         # captured step, Inception-v3 +0.5 % (885 launches per step), VGG-16 +0.2 %; ResNet-50 is
@@ -151,8 +178,10 @@ def main():
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:
+        _dump_outputs(args.dump_outputs, loss, step, net)
     phases = {}
-    if world > 1 and not cpu and not args.graph:
+    if args.full and world > 1 and not cpu and not args.graph:
         # after (outside) the timed region: 3 steps with HIP events on the compute stream.  The
         # "allreduce" section runs from the last backward kernel to the moment the compute stream
         # may proceed past every bucket's collective = the exposed (non-overlapped) all-reduce time.
@@ -199,12 +228,40 @@ def main():
                                              1),
                        # max over ranks, measured after the timed steps (N > 1 only)
                        "phases_ms": phases or None,
+                       # fixed-order reductions (--dump-outputs or DTM_DETERMINISTIC=1): ~5 % slower steps
+                       "deterministic": deterministic,
                        "optimizer": {"momentum": "momentum-sgd+wd", "rmsprop": "rmsprop(TF)+wd", "sgd": "sgd+wd"}[opt],
                        "final_loss": round(float(loss), 4) if math.isfinite(float(loss)) else None},
         }
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()
+
+
+DUMP_SAMPLE = 1 << 20  # elements kept of every dumped vector longer than this (4 MB of float32 each)
+
+
+def _dump_outputs(out_dir, loss, step, net):
+    """Write what the last timed step computed as ``out_dir/<name>.npy`` (float32): the loss it returned, the
+    gradients it left in the flat buffer (as the optimizer read them, all-reduced for N > 1) and the parameters
+    after its update.  Vectors longer than DUMP_SAMPLE keep a fixed sample: the same sorted indices in every run
+    (own seeded generator, independent of the model's and the data's random streams)."""
+    import numpy as np
+    import torch
+
+    def sample(flat):
+        flat = flat.detach().reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            g = torch.Generator().manual_seed(20240)
+            idx = torch.randperm(flat.numel(), generator=g)[:DUMP_SAMPLE].sort().values
+            flat = flat[idx.to(flat.device)]
+        return flat.to(torch.float32).cpu().numpy()
+
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), loss.detach().to(torch.float32).cpu().numpy().reshape(-1))
+    np.save(os.path.join(out_dir, "grads.npy"), sample(step.dp.flat))
+    np.save(os.path.join(out_dir, "params.npy"),
+            sample(torch.cat([p.detach().reshape(-1).to(torch.float32) for p in net.parameters()])))
 
 
 def _free_port():

@@ -226,6 +226,57 @@ def test_bench_refuses_world_size_mismatch():
     assert out.returncode == 2 and "WORLD_SIZE" in out.stderr
 
 
+def test_bench_dump_outputs_and_full(tmp_path):
+    """``--dump-outputs DIR`` writes the last timed step's loss, gradients and updated parameters as float32 .npy
+    files, the same from run to run (seeded inputs; CPU fp32, so only summation order may move the last bits), and
+    ``--full`` keeps the result line's fields and the outputs of a plain run."""
+    import json
+    import os
+    import numpy as np
+    runs = []
+    for name, extra in (("a", []), ("b", ["--full"])):
+        d = tmp_path / name
+        out = _run_bench(["--model", "lenet", "--device", "cpu", "--steps", "3", "--warmup", "1", "--batch", "16",
+                          "--dump-outputs", str(d)] + extra)
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, out.stdout
+        r = json.loads(lines[0])
+        assert r["steps"] == 3 and r["warmup"] == 1 and r["ms_per_step"] > 0 and r["unit"] == "images/sec"
+        assert r["config"]["deterministic"] is None  # (GPU kernels only)
+        assert abs(r["value"] - 16 / (r["ms_per_step"] / 1000.0)) <= 0.01 * r["value"]
+        arrs = {f[:-4]: np.load(str(d / f)) for f in sorted(os.listdir(str(d)))}
+        assert sorted(arrs) == ["grads", "loss", "params"]
+        assert all(a.dtype == np.float32 and a.ndim == 1 and np.isfinite(a).all() for a in arrs.values())
+        assert arrs["loss"].shape == (1,) and abs(float(arrs["loss"][0]) - r["config"]["final_loss"]) < 1e-3
+        assert arrs["grads"].size == arrs["params"].size > 1000 and np.abs(arrs["grads"]).max() > 0
+        assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        runs.append((r, arrs))
+    assert sorted(runs[0][0]) == sorted(runs[1][0])
+    for k in ("loss", "grads", "params"):
+        np.testing.assert_allclose(runs[0][1][k], runs[1][1][k], rtol=1e-4, atol=1e-6)
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_bit_identical_run_to_run(tmp_path):
+    """Two ``--dump-outputs`` runs of the headline model (64^2, batch 16: more than one block per reduction) with
+    the same arguments write bit-identical arrays - the option turns on the kernels' fixed-order reductions and
+    the result line says so."""
+    import json
+    import numpy as np
+    args = ["--model", "resnet_v1_50", "--image-size", "64", "--batch", "16", "--steps", "3", "--warmup", "1"]
+    dumps = []
+    for name in ("a", "b"):
+        out = _run_bench(args + ["--dump-outputs", str(tmp_path / name)])
+        assert out.returncode == 0, out.stderr[-3000:]
+        r = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
+        assert r["config"]["deterministic"] is True and r["steps"] == 3
+        dumps.append({k: np.load(str(tmp_path / name / (k + ".npy"))) for k in ("loss", "grads", "params")})
+    for k, a in dumps[0].items():
+        assert a.dtype == np.float32 and np.isfinite(a).all()
+        assert np.array_equal(a, dumps[1][k]), k
+    assert dumps[0]["grads"].size == 1 << 20 and np.abs(dumps[0]["grads"]).max() > 0
+
 def test_bsp_bucket_layout_small_tail():
     """Buckets cover the flat gradient buffer exactly, at most bucket_mb each, and the last one of
     backward (the first layers' gradients) is cut at tail_mb so the exposed collective is short."""

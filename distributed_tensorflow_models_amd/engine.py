@@ -4,6 +4,7 @@ This is the MI355X replacement for the reference's per-step ``sess.run([train_op
 global_step])``: no PS round trips, gradients reduced over RCCL while backward
 runs, one multi-tensor optimizer launch, TF 1.x optimizer / loss semantics.
 """
+import contextlib
 import os
 
 import torch
@@ -47,6 +48,31 @@ def moving_average_buffers(model):
     from .models.layers import tf_variables
     return [t for _n, t, _l, trainable in tf_variables(model)
             if not trainable and t.dtype == torch.float32 and t.is_floating_point()]
+
+
+@contextlib.contextmanager
+def side_forward(model, device=None, rng=False):
+    """A training-mode forward NEXT TO the training run (the accuracy probe, the activation summaries): the BN
+    moving statistics, which the fused training-mode kernels update in place, are saved on entry and put back on
+    exit.  ``rng``: also put back the dropout seed stream and torch's CPU (and ``device``'s) generator state, so
+    the training run is bit-identical with and without the forward."""
+    bufs = moving_average_buffers(model)
+    saved = [b.detach().clone() for b in bufs]
+    if rng:
+        seed = _elementwise._seed[0]
+        cpu_state = torch.get_rng_state()
+        dev_state = torch.cuda.get_rng_state(device) if (device is not None and device.type == "cuda") else None
+    try:
+        yield
+    finally:
+        with torch.no_grad():
+            for b, v in zip(bufs, saved):
+                b.copy_(v)
+        if rng:
+            _elementwise._seed[0] = seed
+            torch.set_rng_state(cpu_state)
+            if dev_state is not None:
+                torch.cuda.set_rng_state(dev_state, device)
 
 
 def moving_average_decays(model, buffers):

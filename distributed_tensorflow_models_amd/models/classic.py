@@ -47,15 +47,18 @@ class Cifar10CNN(Layer):
                                              ("truncated_normal", 1 / 192.0), 0.0)
 
     def forward(self, x, training=True, end_points=None):
-        net = self.conv1(x, training)
+        # end points: the tensors the reference passes to _activation_summary (cnn/cifar10.py:221-280)
+        ep = end_points if end_points is not None else {}
+        net = ep[_join(self.scope, "conv1")] = self.conv1(x, training)
         net = F.max_pool(net, 3, 2, "SAME")
         net = lrn(net, 4, 1.0, 0.001 / 9.0, 0.75)
-        net = self.conv2(net, training)
+        net = ep[_join(self.scope, "conv2")] = self.conv2(net, training)
         net = lrn(net, 4, 1.0, 0.001 / 9.0, 0.75)
         net = F.max_pool(net, 3, 2, "SAME")
-        net = self.local3(_flatten(net), training)
-        net = self.local4(net, training)
-        return self.softmax_linear(net, training)
+        net = ep[_join(self.scope, "local3")] = self.local3(_flatten(net), training)
+        net = ep[_join(self.scope, "local4")] = self.local4(net, training)
+        net = ep[_join(self.scope, "softmax_linear")] = self.softmax_linear(net, training)
+        return net
 
 
 class LeNet(Layer):
@@ -72,13 +75,18 @@ class LeNet(Layer):
             if num_classes else None
 
     def forward(self, x, training=True, end_points=None):
-        net = F.max_pool(self.conv1(x, training), 2, 2, "VALID")
-        net = F.max_pool(self.conv2(net, training), 2, 2, "VALID")
-        net = self.fc3(_flatten(net), training)
+        # end points as in vgg/nets/lenet.py:63-91
+        ep = end_points if end_points is not None else {}
+        net = ep[_join(self.scope, "conv1")] = self.conv1(x, training)
+        net = ep[_join(self.scope, "pool1")] = F.max_pool(net, 2, 2, "VALID")
+        net = ep[_join(self.scope, "conv2")] = self.conv2(net, training)
+        net = ep[_join(self.scope, "pool2")] = F.max_pool(net, 2, 2, "VALID")
+        net = ep[_join(self.scope, "fc3")] = self.fc3(_flatten(net), training)
         if self.fc4 is None:
             return net
         net = self.dropout3(net, training)
-        return self.fc4(net, training)
+        net = ep[_join(self.scope, "Logits")] = self.fc4(net, training)
+        return net
 
 
 class CifarNet(Layer):

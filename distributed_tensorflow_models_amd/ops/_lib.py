@@ -145,6 +145,14 @@ _SIGS = {
     "dtm_stem_pack": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "dtm_dropout": (_I, [_P, _P, _L, _I, _F, ctypes.c_ulonglong, _P, _P]),
     "dtm_in_top_k": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
+    "dtm_stats_tensor_bytes": (_I, []),
+    "dtm_stats_chunk_bytes": (_I, []),
+    "dtm_stats_partial_bytes": (_I, []),
+    "dtm_stats_result_bytes": (_I, []),
+    "dtm_stats_chunk_size": (_I, []),
+    "dtm_stats_num_buckets": (_I, []),
+    "dtm_stats_limits": (None, [_P]),
+    "dtm_tensor_stats": (_I, [_P, _P, _I, _I, _P, _P, _P, _P]),
 }
 
 

@@ -148,3 +148,30 @@ def lrn(x, depth_radius=5, bias=1.0, alpha=1.0, beta=0.5):
     s = sum(padded[:, i:i + C] for i in range(2 * depth_radius + 1))
     y = xf / (bias + alpha * s.permute(0, 2, 3, 1)) ** beta
     return y.to(x.dtype)
+
+
+def tensor_stats(x, scale=1.0):
+    """Plain oracle of ops.summary.TensorStats for one tensor (tests only): the values v = float(x) * scale in
+    fp32; the bucket of a finite v is the NUMBER of limits <= v, counted by direct comparison in fp64 (= the index
+    of the first limit > v); sum and sum of squares are math.fsum's correctly rounded sums; non-finite values are
+    counted only.  Returns the record dict of TensorStats.fetch()."""
+    import math
+
+    import numpy as np
+
+    from .summary import NUM_BUCKETS, limits
+    if isinstance(x, torch.Tensor):
+        x = x.detach().reshape(-1).float().cpu().numpy()
+    v = np.asarray(x, dtype=np.float32).reshape(-1) * np.float32(scale)
+    fin = v[np.isfinite(v)]
+    d = fin.astype(np.float64)
+    lim = limits()
+    counts = np.zeros(NUM_BUCKETS, dtype=np.uint32)
+    for s in range(0, d.size, 8192):
+        b = (lim[None, :] <= d[s:s + 8192, None]).sum(1)
+        np.add.at(counts, b, 1)
+    return dict(counts=counts, n=int(v.size), num=int(fin.size),
+                min=float(fin.min()) if fin.size else float("inf"),
+                max=float(fin.max()) if fin.size else float("-inf"),
+                sum=math.fsum(d.tolist()), sum_squares=math.fsum((d * d).tolist()),
+                zeros=int(np.count_nonzero(fin == 0)), nonfinite=int(v.size - fin.size))

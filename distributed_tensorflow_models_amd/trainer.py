@@ -124,6 +124,13 @@ def define_common_flags(flags, preset):
             ("save_interval_secs", I, p["save_secs"], "Save interval seconds."),
             ("save_every_steps", I, 0, "also checkpoint every N global steps (0 = time-based only)"),
             ("save_summaries_secs", I, 180, "train-side TensorBoard scalars at most this often (0 = off)"),
+            ("save_summaries_steps", I, 0, "also write the train-side summaries whenever global_step % N == 0, "
+             "on logged steps (0 = time-based only)"),
+            ("summary_histograms", B, False, "histograms of every trainable variable and its gradient "
+             "(<var>, <var>/gradients); the variables are read AFTER the step's update; gradients under BSP only"),
+            ("summary_activations", B, False, "activation histograms and sparsity per end point "
+             "(<end_point>/activations, <end_point>/sparsity): one extra no-grad forward per summary step"),
+            ("summary_images", I, 0, "image summary (images/image/<i>) of the first N images of the input batch"),
             ("initial_learning_rate", Fl, p["lr"], "Initial learning rate."),
             ("num_epochs_per_decay", Fl, p["decay_epochs"], "Epochs after which learning rate decays."),
             ("learning_rate_decay_factor", Fl, p["decay_factor"], "Learning rate decay factor."),
@@ -368,8 +375,15 @@ def train(preset, flags, default_mode="bsp"):
     # cnn/cifar10.py:309-335,361: learning_rate, total_loss (raw) and its 0.9 moving average), written
     # to train_dir by the chief at most every --save_summaries_secs
     from .utils.tb import SummaryWriter
-    tbw = SummaryWriter(FLAGS.train_dir) if (is_chief and FLAGS.save_summaries_secs > 0) else None
+    tbw = SummaryWriter(FLAGS.train_dir) if (is_chief and (FLAGS.save_summaries_secs > 0 or
+                                                           FLAGS.save_summaries_steps > 0)) else None
     loss_avg, t_summary = None, None
+    # histogram / sparsity / image summaries (utils/summaries.py; all off by default)
+    summ = None
+    if tbw is not None and (FLAGS.summary_histograms or FLAGS.summary_activations or FLAGS.summary_images > 0):
+        from .utils.summaries import TrainSummaries
+        summ = TrainSummaries(model, step_fn, mode, FLAGS.summary_histograms, FLAGS.summary_activations,
+                              FLAGS.summary_images)
 
     # ---- loop (reference hot loop) ------------------------------------------------
     step = start if mode == "bsp" else 0
@@ -393,6 +407,15 @@ def train(preset, flags, default_mode="bsp"):
             loss, gs = step_fn(images, labels)
         n_since += 1
         log_now = step % max(FLAGS.log_every, 1) == 0 or step + 1 >= FLAGS.max_steps
+        # a summary step is a logged step on which the time rule or the step rule fires; the device work of the
+        # histogram / activation / image summaries is enqueued here, right after the step (the flat gradient
+        # buffer keeps its values until the next zero_grad), and read after this logged step's synchronisation
+        summ_now = tbw is not None and log_now and (
+            (FLAGS.save_summaries_secs > 0 and
+             (t_summary is None or time.time() - t_summary >= FLAGS.save_summaries_secs)) or
+            (FLAGS.save_summaries_steps > 0 and gs % FLAGS.save_summaries_steps == 0))
+        if summ is not None and summ_now:
+            summ.launch(images)
         # the loss is read (a device sync) on log steps only; the NaN assertion of the reference
         # (imagenet_inception_bsp.py:191, every step) is checked there, and non-finite steps in
         # between are caught by the engine's device-side guard (update skipped, counted, reported)
@@ -423,12 +446,14 @@ def train(preset, flags, default_mode="bsp"):
             print(format_step(cfg["log_style"], step, gs, loss_v, B / max(dt, 1e-9), dt), flush=True)
             if tbw is not None and loss_v == loss_v:
                 loss_avg = loss_v if loss_avg is None else 0.9 * loss_avg + 0.1 * loss_v
-                if t_summary is None or time.time() - t_summary >= FLAGS.save_summaries_secs:
+                if summ_now:
                     t_summary = time.time()
                     tbw.add_scalar("learning_rate", float(sched(gs)), gs)
                     tbw.add_scalar("total_loss (raw)", loss_v, gs)
                     tbw.add_scalar("total_loss", loss_avg, gs)
                     tbw.add_scalar("images_per_sec", world * B / max(dt, 1e-9), gs)
+            if summ is not None and summ_now:
+                summ.write(tbw, gs)
             extra = step_fn.timer.sections() if (mode == "bsp" and step_fn.timer is not None) else {}
             if mode == "bsp" and metrics.f is not None and world > 1:
                 bms = step_fn.dp.bucket_ms()  # per-bucket all-reduce durations (RCCL timing events)
@@ -472,18 +497,14 @@ def train_accuracy_probe(model, data):
     network in TRAINING mode (batch statistics), whose BN moving averages that sess.run leaves alone (the
     reference never runs UPDATE_OPS there).  Here the moving statistics are saved and restored around the
     forward (the fused training-mode kernels update them in place)."""
-    from .engine import moving_average_buffers
-    bufs = moving_average_buffers(model)
-    saved = [b.detach().clone() for b in bufs]
+    from .engine import side_forward
     images, labels = data.next_batch()
-    with torch.no_grad():
+    with side_forward(model), torch.no_grad():
         out = model(images, training=True)
         if isinstance(out, tuple):
             out = out[0]
         from .ops.lazy import as_tensor
         acc = (as_tensor(out).float().argmax(-1) == labels).float().mean().item()
-        for b, v in zip(bufs, saved):
-            b.copy_(v)
     return acc
 
 

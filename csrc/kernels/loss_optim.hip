@@ -9,7 +9,9 @@
 //   SGD            p -= lr*g
 //   Momentum       a = mu*a + g;  p -= lr*a            (use_nesterov=False)
 //   RMSProp (TF)   ms = rho*ms + (1-rho)*g^2;  mom = mu*mom + lr*g/sqrt(ms+eps);  p -= mom
-// with g = grad*grad_scale + wd*p (coupled L2, the gradient of wd*sum(p^2)/2), an optional
+//   LARS           the Momentum update with the rate lr*lr_scale[t] (trust ratio from the norm pass below)
+// with g = grad*grad_scale + wd*p (coupled L2, the gradient of wd*sum(p^2)/2), optionally times the
+// clip-by-global-norm factor of the norm pass, an optional
 // fused ExponentialMovingAverage shadow update (decay already min'd with (1+n)/(10+n) on the
 // host) and a bf16 copy-out of the updated weight for the next forward.
 #include "common.h"
@@ -95,6 +97,8 @@ struct OptHyper {
   int use_ema;
   const int* skip_flag;  // optional: non-zero -> skip the update (non-finite gradients)
   const float* dyn;      // optional device scalars [lr, ema_decay, grad_scale] (graph-replay safe)
+  const float* lr_scale;  // optional per-tensor rate factor (LARS trust ratio) written by the norm pass
+  const float* gclip;     // optional scalar gradient factor (clip by global norm) written by the norm pass
 };
 constexpr int OPT_CHUNK = 8192;
 
@@ -104,7 +108,9 @@ __global__ __launch_bounds__(256) void multi_tensor_opt_kernel(const OptTensor* 
   const OptChunk c = chunks[blockIdx.x];
   const OptTensor t = tens[c.t];
   const long end = min(t.n, c.start + (long)OPT_CHUNK);
-  const float lr = (h.dyn ? h.dyn[0] : h.lr) * t.lr_mult;
+  float lr = (h.dyn ? h.dyn[0] : h.lr) * t.lr_mult;
+  if (h.lr_scale) lr *= h.lr_scale[c.t];
+  const float gclip = h.gclip ? h.gclip[0] : 1.f;
   const float ema_decay = h.dyn ? h.dyn[1] : h.ema_decay;
   const float grad_scale = h.dyn ? h.dyn[2] : h.grad_scale;
   if (!t.g) {  // EMA-only row (BN moving statistics): shadow -= (1-d)(shadow - value)
@@ -115,6 +121,7 @@ __global__ __launch_bounds__(256) void multi_tensor_opt_kernel(const OptTensor* 
   for (long i = c.start + threadIdx.x; i < end; i += 256) {
     float p = t.p[i];
     float g = t.g[i] * grad_scale + t.wd * p;
+    if (h.gclip) g *= gclip;
     if (h.kind == 0) {
       p -= lr * g;
     } else if (h.kind == 1) {
@@ -131,6 +138,129 @@ __global__ __launch_bounds__(256) void multi_tensor_opt_kernel(const OptTensor* 
     t.p[i] = p;
     if (t.pcopy) t.pcopy[i] = f2bf(p);
     if (h.use_ema && t.ema) t.ema[i] -= (1.f - ema_decay) * (t.ema[i] - p);
+  }
+}
+
+// ---- multi-tensor norm pass (LARS trust ratios, clipping by global norm) -------------------------------------
+// The L2 norms of every weight and every reduced gradient in two launches over the optimizer's own tables, with no
+// float atomics, flags or inter-block waiting: the kernel boundary is the only synchronisation, and every sum has a
+// fixed order, so the results are bit-identical run to run and rank to rank (replicas that derived different trust
+// ratios from the same all-reduced gradient would drift apart).
+//   launch 1: one block per OptChunk row -> one record {sum p^2, sum gs^2, sum ge^2} (fp64), with
+//             gs = g*grad_scale and ge = g*grad_scale + wd*p, the update kernel's own fp32 expressions;
+//   launch 2: one block; per tensor the records are summed (lane l takes records l, l+64, ... in chunk order, then a
+//             xor butterfly over the wave), then the per-tensor sum ge^2 the same way in tensor order:
+//     norms[t]    = {|p|, |gs|, |ge|}
+//     lr_scale[t] = eeta*|p| / (|gs| + wd_t*|p| + eps)  if tensor t is adapted, |p| > 0 and |gs| > 0, else 1   (LARS)
+//     gclip       = clip / max(sqrt(sum_t sum ge^2), clip)  if clip > 0, else 1            (tf.clip_by_global_norm)
+struct NormRec {
+  double p2, gs2, ge2;
+};
+struct NormMeta {  // per tensor, beside the 64-byte OptTensor: its rows of the chunk table and the LARS flag
+  int chunk0, nchunks, adapt, pad;
+};
+struct NormHyper {
+  float grad_scale, eeta, eps, clip;
+  const float* dyn;  // optional device scalars [lr, ema_decay, grad_scale], as OptHyper::dyn
+};
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+__device__ __forceinline__ void norm_add(NormRec& a, float p, float g, float grad_scale, float wd) {
+  const float gs = g * grad_scale;
+  const float ge = g * grad_scale + wd * p;
+  a.p2 += (double)p * (double)p;
+  a.gs2 += (double)gs * (double)gs;
+  a.ge2 += (double)ge * (double)ge;
+}
+
+__global__ __launch_bounds__(256) void multi_tensor_norm_kernel(const OptTensor* __restrict__ tens,
+                                                                const OptChunk* __restrict__ chunks, NormHyper h,
+                                                                NormRec* __restrict__ recs) {
+  __shared__ double red[4][3];
+  const int tid = threadIdx.x;
+  const OptChunk c = chunks[blockIdx.x];
+  const OptTensor t = tens[c.t];
+  NormRec a = {0.0, 0.0, 0.0};
+  if (t.g) {  // (an EMA-only row writes a zero record)
+    const float grad_scale = h.dyn ? h.dyn[2] : h.grad_scale;
+    const long rem = t.n - c.start;
+    const int len = (int)(rem < (long)OPT_CHUNK ? (rem > 0 ? rem : 0) : (long)OPT_CHUNK);
+    const float* pp = t.p + c.start;
+    const float* gp = t.g + c.start;
+    if ((((uintptr_t)pp ^ (uintptr_t)gp) & 15u) == 0) {
+      // weight and gradient reach a 16-byte boundary together: a scalar head up to it, 16-byte loads over the
+      // body, a scalar tail (gradients are views into the flat all-reduce buffer at any element offset)
+      int head = (int)(((16u - (unsigned)((uintptr_t)gp & 15u)) & 15u) >> 2);
+      head = head < len ? head : len;
+      const int nvec = (len - head) >> 2, tail0 = head + (nvec << 2);
+      if (tid < head) norm_add(a, pp[tid], gp[tid], grad_scale, t.wd);
+      const f32x4* pv = (const f32x4*)(pp + head);
+      const f32x4* gv = (const f32x4*)(gp + head);
+      for (int i = tid; i < nvec; i += 256) {
+        const f32x4 pw = pv[i], gw = gv[i];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) norm_add(a, pw[e], gw[e], grad_scale, t.wd);
+      }
+      if (tail0 + tid < len) norm_add(a, pp[tail0 + tid], gp[tail0 + tid], grad_scale, t.wd);
+    } else {  // the two are offset against each other within 16 bytes: coalesced 4-byte loads
+      for (int i = tid; i < len; i += 256) norm_add(a, pp[i], gp[i], grad_scale, t.wd);
+    }
+  }
+  // fixed order: xor butterfly over each wave, then the four waves in LDS
+  a.p2 = wave_sum_f64(a.p2);
+  a.gs2 = wave_sum_f64(a.gs2);
+  a.ge2 = wave_sum_f64(a.ge2);
+  if ((tid & 63) == 0) {
+    red[tid >> 6][0] = a.p2; red[tid >> 6][1] = a.gs2; red[tid >> 6][2] = a.ge2;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    NormRec r;
+    r.p2 = (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]);
+    r.gs2 = (red[0][1] + red[1][1]) + (red[2][1] + red[3][1]);
+    r.ge2 = (red[0][2] + red[1][2]) + (red[2][2] + red[3][2]);
+    recs[blockIdx.x] = r;
+  }
+}
+
+constexpr int NORM_FIN_THREADS = 1024;
+__global__ __launch_bounds__(NORM_FIN_THREADS) void multi_tensor_norm_finalize_kernel(
+    const OptTensor* __restrict__ tens, const NormMeta* __restrict__ meta, int ntens,
+    const NormRec* __restrict__ recs, NormHyper h, double* __restrict__ tsum, float* __restrict__ norms,
+    float* __restrict__ lr_scale, float* __restrict__ gclip) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  for (int t = wv; t < ntens; t += NORM_FIN_THREADS / 64) {  // one wave per tensor
+    const NormMeta m = meta[t];
+    double p2 = 0.0, gs2 = 0.0, ge2 = 0.0;
+    for (int j = lane; j < m.nchunks; j += 64) {
+      const NormRec r = recs[m.chunk0 + j];
+      p2 += r.p2; gs2 += r.gs2; ge2 += r.ge2;
+    }
+    p2 = wave_sum_f64(p2);
+    gs2 = wave_sum_f64(gs2);
+    ge2 = wave_sum_f64(ge2);
+    if (lane == 0) {
+      const double pn = sqrt(p2), gn = sqrt(gs2);
+      norms[3 * t] = (float)pn;
+      norms[3 * t + 1] = (float)gn;
+      norms[3 * t + 2] = (float)sqrt(ge2);
+      double s = 1.0;
+      if (m.adapt && pn > 0.0 && gn > 0.0) s = (double)h.eeta * pn / (gn + (double)tens[t].wd * pn + (double)h.eps);
+      lr_scale[t] = (float)s;
+      tsum[t] = ge2;
+    }
+  }
+  __syncthreads();
+  if (wv == 0) {
+    double s = 0.0;
+    for (int t = lane; t < ntens; t += 64) s += tsum[t];
+    s = wave_sum_f64(s);
+    if (lane == 0) gclip[0] = h.clip > 0.f ? (float)((double)h.clip / fmax(sqrt(s), (double)h.clip)) : 1.f;
   }
 }
 
@@ -231,16 +361,55 @@ DTM_API int dtm_opt_chunk_size() { return OPT_CHUNK; }
 DTM_API int dtm_opt_tensor_bytes() { return (int)sizeof(OptTensor); }
 DTM_API int dtm_opt_chunk_bytes() { return (int)sizeof(OptChunk); }
 
-DTM_API void dtm_multi_tensor_opt(const void* tensors_dev, const void* chunks_dev, int num_chunks, int kind, float lr,
-                                  float mu, float rho, float eps, float grad_scale, float ema_decay, int use_ema,
-                                  const int* skip_flag, const float* dyn, void* stream) {
+// lr_scale [ntens] / gclip [1]: the outputs of dtm_multi_tensor_norms (either may be null: factor 1)
+DTM_API void dtm_multi_tensor_opt_scaled(const void* tensors_dev, const void* chunks_dev, int num_chunks, int kind,
+                                         float lr, float mu, float rho, float eps, float grad_scale, float ema_decay,
+                                         int use_ema, const int* skip_flag, const float* dyn, const float* lr_scale,
+                                         const float* gclip, void* stream) {
   OptHyper h;
   h.dyn = dyn;
   h.kind = kind; h.lr = lr; h.mu = mu; h.rho = rho; h.eps = eps; h.grad_scale = grad_scale;
   h.ema_decay = ema_decay; h.use_ema = use_ema; h.skip_flag = skip_flag;
+  h.lr_scale = lr_scale; h.gclip = gclip;
   if (num_chunks <= 0) return;
   hipLaunchKernelGGL(multi_tensor_opt_kernel, dim3(num_chunks), dim3(256), 0, (hipStream_t)stream,
                      (const OptTensor*)tensors_dev, (const OptChunk*)chunks_dev, h);
+}
+
+DTM_API void dtm_multi_tensor_opt(const void* tensors_dev, const void* chunks_dev, int num_chunks, int kind, float lr,
+                                  float mu, float rho, float eps, float grad_scale, float ema_decay, int use_ema,
+                                  const int* skip_flag, const float* dyn, void* stream) {
+  dtm_multi_tensor_opt_scaled(tensors_dev, chunks_dev, num_chunks, kind, lr, mu, rho, eps, grad_scale, ema_decay,
+                              use_ema, skip_flag, dyn, nullptr, nullptr, stream);
+}
+
+DTM_API int dtm_opt_norm_meta_bytes() { return (int)sizeof(NormMeta); }
+// bytes of the norm pass's scratch: one record per chunk row, then one fp64 sum per tensor
+DTM_API long dtm_opt_norm_scratch_bytes(int num_chunks, int ntens) {
+  return (long)sizeof(NormRec) * (num_chunks > 0 ? num_chunks : 0) + (long)sizeof(double) * (ntens > 0 ? ntens : 0);
+}
+
+// The two-launch norm pass over the optimizer's tables (tensors_dev / chunks_dev as dtm_multi_tensor_opt; meta_dev:
+// ntens NormMeta rows; the chunk rows of a tensor are contiguous and in order).  Writes norms [ntens][3], lr_scale
+// [ntens], gclip [1]; nothing is allocated or uploaded, so the pass can be captured into a hipGraph.
+DTM_API int dtm_multi_tensor_norms(const void* tensors_dev, const void* chunks_dev, int num_chunks,
+                                   const void* meta_dev, int ntens, const float* dyn, float grad_scale, float eeta,
+                                   float eps, float clip, void* scratch, float* norms, float* lr_scale, float* gclip,
+                                   void* stream) {
+  if (num_chunks < 0 || ntens <= 0 || !tensors_dev || !meta_dev || !scratch || !norms || !lr_scale || !gclip)
+    return -1;
+  if (num_chunks > 0 && !chunks_dev) return -1;
+  NormHyper h;
+  h.grad_scale = grad_scale; h.eeta = eeta; h.eps = eps; h.clip = clip; h.dyn = dyn;
+  NormRec* recs = (NormRec*)scratch;
+  double* tsum = (double*)(recs + num_chunks);
+  if (num_chunks > 0)
+    hipLaunchKernelGGL(multi_tensor_norm_kernel, dim3(num_chunks), dim3(256), 0, (hipStream_t)stream,
+                       (const OptTensor*)tensors_dev, (const OptChunk*)chunks_dev, h, recs);
+  hipLaunchKernelGGL(multi_tensor_norm_finalize_kernel, dim3(1), dim3(NORM_FIN_THREADS), 0, (hipStream_t)stream,
+                     (const OptTensor*)tensors_dev, (const NormMeta*)meta_dev, ntens, (const NormRec*)recs, h, tsum,
+                     norms, lr_scale, gclip);
+  return 0;
 }
 
 DTM_API void dtm_check_finite(const float* x, long n, int* flag, void* stream) {

@@ -4,7 +4,9 @@
   the text ``checkpoint`` state file (``model_checkpoint_path`` / ``all_model_checkpoint_paths``)
   that evaluators poll (reference cnn/cifar10_eval.py:72-80, inception/inception_eval.py:68-81);
 * TF variable names and layouts: conv kernels are exported HWIO ([R,S,C,K]) from the internal
-  [K,R,S,C]; optimizer slots ``<v>/Momentum``, ``<v>/RMSProp``, ``<v>/RMSProp_1``; EMA shadows
+  [K,R,S,C]; optimizer slots ``<v>/Momentum`` (momentum, and LARS: the two resume into each other; the slot name
+  of TensorFlow's own contrib LARS optimizer is not checked here, TensorFlow is not part of the test environment),
+  ``<v>/RMSProp``, ``<v>/RMSProp_1``; EMA shadows
   ``<v>/ExponentialMovingAverage``; ``global_step`` int64;
 * ``max_to_keep`` retention; writes are atomic (tempstate + rename in the native writer);
 * the ``.meta`` GraphDef is not produced (there is no TF graph) - documented deviation.
@@ -74,7 +76,7 @@ def model_variables(model, optimizer=None, global_step=None, include_slots=True,
             if base is None:
                 continue
             st = optimizer.state[p]
-            if optimizer.kind == "momentum":
+            if optimizer.kind in ("momentum", "lars"):  # LARS keeps the momentum slot and its name
                 out.append(TFVar(base.name + "/Momentum", st["s1"], base.layout, partitions))
             elif optimizer.kind == "rmsprop":
                 out.append(TFVar(base.name + "/RMSProp", st["s2"], base.layout, partitions))

@@ -96,6 +96,54 @@ class ExponentialDecay:
         return exponential_decay(self.lr, step, self.steps, self.rate, self.staircase)
 
 
+def polynomial_decay(learning_rate, global_step, decay_steps, end_learning_rate=0.0001, power=1.0, cycle=False,
+                     name=None):
+    """tf.train.polynomial_decay: (lr - end) * (1 - min(step, decay_steps)/decay_steps)^power + end; with ``cycle``
+    the step is not clamped and decay_steps is multiplied by ceil(step/decay_steps) (1 at step 0) instead.
+
+    An int step gives the value; the global-step TENSOR gives a ``DecayedLearningRate`` bound to it, as
+    ``exponential_decay`` does."""
+    if torch.is_tensor(global_step):
+        return DecayedLearningRate(PolynomialDecay(learning_rate, decay_steps, end_learning_rate, power, cycle),
+                                   global_step)
+    step, decay_steps = float(int(global_step)), float(decay_steps)
+    if cycle:
+        decay_steps *= 1.0 if step == 0 else math.ceil(step / decay_steps)
+    else:
+        step = min(step, decay_steps)
+    return (learning_rate - end_learning_rate) * (1.0 - step / decay_steps) ** power + end_learning_rate
+
+
+class PolynomialDecay:
+    """Schedule object (callable on the step) with the semantics of ``polynomial_decay``."""
+
+    def __init__(self, learning_rate, decay_steps, end_learning_rate=0.0001, power=1.0, cycle=False):
+        self.lr, self.steps, self.end, self.power, self.cycle = learning_rate, decay_steps, end_learning_rate, power, \
+            cycle
+
+    def __call__(self, step):
+        return polynomial_decay(self.lr, step, self.steps, self.end, self.power, self.cycle)
+
+
+class LinearWarmup:
+    """Linear warm-up in front of a schedule (a callable on the step, or a constant rate): for step < warmup_steps
+    the rate goes linearly from ``start_lr`` at step 0 to ``schedule(warmup_steps)``; from warmup_steps on it is
+    ``schedule(step)``."""
+
+    def __init__(self, schedule, warmup_steps, start_lr=0.0):
+        self.schedule, self.warmup_steps, self.start_lr = schedule, int(warmup_steps), float(start_lr)
+
+    def _after(self, step):
+        return float(self.schedule(step)) if callable(self.schedule) else float(self.schedule)
+
+    def __call__(self, step):
+        step = int(step)
+        if step >= self.warmup_steps:
+            return self._after(step)
+        target = self._after(self.warmup_steps)
+        return self.start_lr + (target - self.start_lr) * step / float(self.warmup_steps)
+
+
 class DecayedLearningRate:
     """A schedule bound to a global-step tensor: ``float(lr)`` = the value at the tensor's current step,
     ``lr(step)`` = the value at ``step``."""
@@ -174,6 +222,18 @@ class MomentumOptimizer(Optimizer):
         if use_nesterov:
             raise NotImplementedError("use_nesterov=True (reference never uses it)")
         super().__init__(learning_rate, momentum=momentum)
+
+
+class LARSOptimizer(Optimizer):
+    """Layer-wise adaptive rate scaling over the momentum update (ops/optim.py): per variable the rate is
+    lr * eeta*|w| / (|g| + weight_decay*|w| + epsilon); variables of rank <= 1 (biases, BN beta / gamma) keep lr.
+    ``weight_decay``: the coupled L2 coefficient of every trainable variable (None: each variable keeps its own
+    ``weight_decay`` attribute, e.g. the model's regularizers).  BSP / single-worker only."""
+    kind = "lars"
+
+    def __init__(self, learning_rate, momentum=0.9, weight_decay=None, eeta=0.001, epsilon=0.0):
+        super().__init__(learning_rate, momentum=momentum, lars_eeta=eeta, lars_epsilon=epsilon)
+        self.weight_decay = weight_decay
 
 
 class RMSPropOptimizer(Optimizer):
@@ -362,11 +422,13 @@ class TrainOp:
       * one worker -> the same TrainStep on one rank.
     ``weight_decay``: the reference's ``wd * add_n(l2_loss(v) for v in trainable_variables())`` term,
     applied as the identical coupled gradient term inside the fused optimizer (an explicit L2 term in
-    the loss callable works too, through autograd, just slower).  The learning rate may be a float or
-    the ``DecayedLearningRate`` returned by ``exponential_decay(lr, global_step_tensor, ...)``."""
+    the loss callable works too, through autograd, just slower).  ``clip_global_norm``: the threshold of a
+    ``tf.clip_by_global_norm`` between compute_gradients and apply_gradients (BSP only).  The learning rate may be a
+    float or the ``DecayedLearningRate`` returned by ``exponential_decay(lr, global_step_tensor, ...)`` /
+    ``polynomial_decay(...)``, or any schedule object (``LinearWarmup(PolynomialDecay(...), n)``)."""
 
     def __init__(self, optimizer, grads, global_step=None, weight_decay=None, bucket_mb=32.0, label_smoothing=0.0,
-                 input_fn=None):
+                 input_fn=None, clip_global_norm=None):
         from ..engine import TrainStep
         from ..parallel import process_group as pg
         sync = isinstance(optimizer, SyncReplicasOptimizer)
@@ -378,11 +440,17 @@ class TrainOp:
         self.mode = "bsp" if (sync or self.world == 1) else "asp"
         lr = base.learning_rate
         sched = lr if callable(lr) else None
-        lr0 = float(lr(0) if isinstance(lr, DecayedLearningRate) else lr)
+        lr0 = float(lr(0) if callable(lr) else lr)
         if isinstance(lr, DecayedLearningRate):
             sched = lr.schedule  # evaluated at the engine's own step counter
         kw = base.config()
         kw.pop("optimizer", None), kw.pop("lr", None)
+        if (base.kind == "lars" or clip_global_norm) and self.mode != "bsp":
+            raise ValueError("LARSOptimizer and clip_global_norm need the BSP step (SyncReplicasOptimizer or one "
+                             "worker): under ASP the update runs on owner shards from one worker's push, where no "
+                             "global gradient norm exists")
+        if weight_decay is None:
+            weight_decay = getattr(base, "weight_decay", None)
         if weight_decay is not None:
             for p in trainable_variables(self.model):
                 p.weight_decay = float(weight_decay)
@@ -398,7 +466,8 @@ class TrainOp:
                                   label_smoothing=label_smoothing, batch_weight=grads.weight,
                                   ema_decay=ema.decay if ema is not None else None, ema_buffers=ema_buffers,
                                   momentum=kw.get("momentum", 0.9), rho=kw.get("rho", 0.9),
-                                  epsilon=kw.get("epsilon", 1e-10))
+                                  epsilon=kw.get("epsilon", 1e-10), lars_eeta=kw.get("lars_eeta", 0.001),
+                                  lars_epsilon=kw.get("lars_epsilon", 0.0), clip_global_norm=clip_global_norm)
             self.step.loss_fn = self._loss
             self.store = None
         else:

@@ -109,7 +109,8 @@ class TrainStep:
                  label_smoothing=0.0, aux_weight=0.4, ema_decay=None, lr_schedule=None, use_graph=False,
                  process_group=None, weight_decay=None, batch_weight=1.0, nan_guard=True, timer=None,
                  grad_comm_dtype=None, ema_buffers=True, bn_sync_every=1, wgrad_stream=None, bsp_check=None,
-                 overlap=True, force_comm=False, graph_comm=False):
+                 overlap=True, force_comm=False, graph_comm=False, lars_eeta=0.001, lars_epsilon=0.0,
+                 clip_global_norm=None):
         self.model = model
         if wgrad_stream is not None:
             # conv+BN weight gradients on the side stream (ops/_lib.py side_stream; process-wide): ResNet-50
@@ -138,7 +139,8 @@ class TrainStep:
         # moving_average_variables(); tf.layers BN - the CIFAR ResNet preset - does not)
         self.opt = FusedOptimizer(params, optimizer, lr, momentum, rho, epsilon, ema_decay, weight_decay,
                                   ema_buffers=moving_average_buffers(model)
-                                  if (ema_decay is not None and ema_buffers) else ())
+                                  if (ema_decay is not None and ema_buffers) else (),
+                                  lars_eeta=lars_eeta, lars_epsilon=lars_epsilon, clip_global_norm=clip_global_norm)
         self.lr = lr
         self.lr_schedule = lr_schedule
         self.smoothing = label_smoothing

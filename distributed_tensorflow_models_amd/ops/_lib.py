@@ -105,6 +105,10 @@ _SIGS = {
     "dtm_opt_tensor_bytes": (_I, []),
     "dtm_opt_chunk_bytes": (_I, []),
     "dtm_multi_tensor_opt": (None, [_P, _P, _I, _I, _F, _F, _F, _F, _F, _F, _I, _P, _P, _P]),
+    "dtm_multi_tensor_opt_scaled": (None, [_P, _P, _I, _I, _F, _F, _F, _F, _F, _F, _I, _P, _P, _P, _P, _P]),
+    "dtm_opt_norm_meta_bytes": (_I, []),
+    "dtm_opt_norm_scratch_bytes": (_L, [_I, _I]),
+    "dtm_multi_tensor_norms": (_I, [_P, _P, _I, _P, _I, _P, _F, _F, _F, _F, _P, _P, _P, _P, _P]),
     "dtm_check_finite": (None, [_P, _L, _P, _P]),
     "dtm_f32_to_bf16": (None, [_P, _P, _L, _P]),
     "dtm_scale": (None, [_P, _L, _F, _P]),

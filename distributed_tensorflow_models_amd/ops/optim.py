@@ -5,25 +5,40 @@ TF 1.x update semantics:
   MomentumOptimizer         a = mu*a + g; p -= lr*a   (use_nesterov=False)  (C20b)
   RMSPropOptimizer          ms = rho*ms + (1-rho)g^2 (ms init 1.0); mom = mu*mom + lr*g/sqrt(ms+eps);
                             p -= mom                                       (C21)
+  LARS (You, Gitman, Ginsburg 2017, in the form of TF 1.x's contrib optimizer): the Momentum update with the
+                            rate lr*lr_scale[t]:  a = mu*a + g; p -= lr*lr_scale[t]*a, where
+                            lr_scale[t] = eeta*|p| / (|gs| + wd_t*|p| + eps)  for an adapted tensor with |p| > 0
+                            and |gs| > 0 (gs = grad*grad_scale), 1 otherwise; tensors with ndim <= 1 (biases, BN
+                            beta / gamma) are not adapted
   g = grad*grad_scale + weight_decay*p   (coupled L2 = d/dp of wd*sum(p^2)/2; K14)
+  clip_global_norm (tf.clip_by_global_norm): g *= clip / max(sqrt(sum over all tensors of |g|^2), clip); the L2
+                            term is part of g because the reference puts it in the loss
   optional ExponentialMovingAverage shadows: ema -= (1-d)(ema - p), d = min(decay,(1+n)/(10+n)) (C22)
 and a bf16 copy-out of every updated weight (the compute copy read by the conv kernels).
+
+The norms LARS and clipping need come from one two-launch multi-tensor pass on the device (fp64 sums in a fixed
+order: bit-identical on every rank), enqueued before the update; the host never waits for them.
 
 On CPU the same math runs as torch ops (gloo plumbing tests, reference checks).
 """
 import ctypes
+import math
 
 import numpy as np
 import torch
 
 from . import _lib
 
-KINDS = {"sgd": 0, "momentum": 1, "rmsprop": 2}
+# kernel update rule per kind (LARS is the momentum rule with a per-tensor rate factor)
+KINDS = {"sgd": 0, "momentum": 1, "rmsprop": 2, "lars": 1}
 
 
 class FusedOptimizer:
     def __init__(self, params, kind="momentum", lr=0.1, momentum=0.9, rho=0.9, epsilon=1e-10, ema_decay=None,
-                 weight_decay=None, lr_mults=None, ema_buffers=()):
+                 weight_decay=None, lr_mults=None, ema_buffers=(), lars_eeta=0.001, lars_epsilon=0.0,
+                 clip_global_norm=None, lars_skip=None):
+        """``lars_skip``: predicate on a parameter, True = its rate is not adapted (default: ``p.ndim <= 1``).
+        ``clip_global_norm``: threshold of the clip by global norm (None or 0: off); not combined with LARS."""
         self.params = [p for p in params if p.requires_grad]
         # non-trainable tensors that also get an EMA shadow (BN moving mean/variance: the reference
         # averages trainable_variables() + moving_average_variables(), e.g. reference
@@ -32,13 +47,22 @@ class FusedOptimizer:
         self.buffer_ema = {id(b): b.detach().clone().float() for b in self.ema_buffers}
         if kind not in KINDS:
             raise ValueError(kind)
+        clip = float(clip_global_norm) if clip_global_norm else 0.0
+        if clip < 0.0:
+            raise ValueError("clip_global_norm must be positive, got %r" % (clip_global_norm,))
+        if kind == "lars" and clip > 0.0:
+            raise ValueError("LARS and clip_global_norm are not combined (the order of the two is not defined)")
         self.kind, self.lr, self.mu, self.rho, self.eps = kind, lr, momentum, rho, epsilon
+        self.lars_eeta, self.lars_eps, self.clip = float(lars_eeta), float(lars_epsilon), clip
+        self.scaled = kind == "lars" or clip > 0.0  # the step needs the norm pass
+        if lars_skip is None:
+            lars_skip = lambda p: p.ndim <= 1  # noqa: E731
         self.ema_decay = ema_decay
         self.num_updates = 0
         self.state = {}
         for p in self.params:
             st = {}
-            if kind in ("momentum", "rmsprop"):
+            if kind in ("momentum", "rmsprop", "lars"):
                 st["s1"] = torch.zeros_like(p, dtype=torch.float32)
             if kind == "rmsprop":
                 st["s2"] = torch.ones_like(p, dtype=torch.float32)  # TF RMSProp ms slot init 1.0
@@ -46,8 +70,15 @@ class FusedOptimizer:
                 st["ema"] = p.detach().clone().float()
             st["wd"] = float(getattr(p, "weight_decay", 0.0) if weight_decay is None else weight_decay)
             st["lr_mult"] = 1.0 if lr_mults is None else float(lr_mults.get(p, 1.0))
+            st["adapt"] = kind == "lars" and not lars_skip(p)
             self.state[p] = st
         self._dev = None
+        self._norms = self._lr_scale = self._gclip = None
+        if self.scaled and not (self.params and self.params[0].is_cuda):
+            n = len(self.params) + len(self.ema_buffers)
+            self._norms = torch.zeros((n, 3), dtype=torch.float32)
+            self._lr_scale = torch.ones(n, dtype=torch.float32)
+            self._gclip = torch.ones(1, dtype=torch.float32)
         if self.params and self.params[0].is_cuda:
             self._build_tables()
 
@@ -92,6 +123,26 @@ class FusedOptimizer:
         self._tens_dev = torch.from_numpy(tens.view(np.uint8).reshape(-1).copy()).to(dev)
         self._chunks_dev = torch.from_numpy(ct.view(np.uint8).reshape(-1).copy()).to(dev)
         self._nchunks = len(chunks)
+        if self.scaled:
+            # the norm pass: a side table beside the 64-byte tensor rows (first chunk row, row count, LARS flag),
+            # its scratch (one fp64 record per chunk row) and its outputs - all allocated here, none in launch()
+            ntens = tens.shape[0]
+            assert L.dtm_opt_norm_meta_bytes() == 16
+            meta = np.zeros((ntens, 4), dtype=np.int32)
+            for j, (i, _, _s) in enumerate(chunks):
+                if meta[i, 1] == 0:
+                    meta[i, 0] = j
+                assert meta[i, 0] + meta[i, 1] == j, "chunk rows of a tensor must be contiguous"
+                meta[i, 1] += 1
+            for i, p in enumerate(self.params):
+                meta[i, 2] = int(self.state[p]["adapt"])
+            self._ntens = ntens
+            self._meta_dev = torch.from_numpy(meta.view(np.uint8).reshape(-1).copy()).to(dev)
+            self._norm_scratch = torch.zeros(int(L.dtm_opt_norm_scratch_bytes(len(chunks), ntens)) // 8,
+                                             dtype=torch.float64, device=dev)
+            self._norms = torch.zeros((ntens, 3), dtype=torch.float32, device=dev)
+            self._lr_scale = torch.ones(ntens, dtype=torch.float32, device=dev)
+            self._gclip = torch.ones(1, dtype=torch.float32, device=dev)
         self._dyn = torch.zeros(3, dtype=torch.float32, device=dev)
         # ring of pinned staging rows: the host runs ahead of the GPU, so a row is reused only
         # after the copy that last read it has executed (its event), never overwritten in flight
@@ -133,10 +184,53 @@ class FusedOptimizer:
     def launch(self, skip_flag=None):
         """Issue the fused update reading lr/ema/grad_scale from the device scalars."""
         L = _lib.lib()
-        L.dtm_multi_tensor_opt(_lib.ptr(self._tens_dev), _lib.ptr(self._chunks_dev), self._nchunks, KINDS[self.kind],
-                               0.0, float(self.mu), float(self.rho), float(self.eps), 1.0, 0.0,
-                               int(self.ema_decay is not None), _lib.ptr(skip_flag), _lib.ptr(self._dyn),
-                               _lib.stream_ptr())
+        if not self.scaled:
+            L.dtm_multi_tensor_opt(_lib.ptr(self._tens_dev), _lib.ptr(self._chunks_dev), self._nchunks,
+                                   KINDS[self.kind], 0.0, float(self.mu), float(self.rho), float(self.eps), 1.0, 0.0,
+                                   int(self.ema_decay is not None), _lib.ptr(skip_flag), _lib.ptr(self._dyn),
+                                   _lib.stream_ptr())
+            return
+        # norm pass (two launches), then the update reading the trust ratios / the clip factor it wrote
+        self.launch_norms()
+        L.dtm_multi_tensor_opt_scaled(_lib.ptr(self._tens_dev), _lib.ptr(self._chunks_dev), self._nchunks,
+                                      KINDS[self.kind], 0.0, float(self.mu), float(self.rho), float(self.eps), 1.0,
+                                      0.0, int(self.ema_decay is not None), _lib.ptr(skip_flag), _lib.ptr(self._dyn),
+                                      _lib.ptr(self._lr_scale) if self.kind == "lars" else None,
+                                      _lib.ptr(self._gclip) if self.clip > 0.0 else None, _lib.stream_ptr())
+
+    def launch_norms(self):
+        """Issue the two-launch norm pass alone (norms, trust ratios and clip factor of the current weights and
+        gradients, with grad_scale from the device scalars); ``launch()`` runs it before the update."""
+        rc = _lib.lib().dtm_multi_tensor_norms(
+            _lib.ptr(self._tens_dev), _lib.ptr(self._chunks_dev), self._nchunks, _lib.ptr(self._meta_dev),
+            self._ntens, _lib.ptr(self._dyn), 1.0, self.lars_eeta, self.lars_eps, self.clip,
+            _lib.ptr(self._norm_scratch), _lib.ptr(self._norms), _lib.ptr(self._lr_scale), _lib.ptr(self._gclip),
+            _lib.stream_ptr())
+        if rc != 0:
+            raise RuntimeError("dtm_multi_tensor_norms failed (%d)" % rc)
+
+    def last_norms(self):
+        """The device tensor [ntens, 3] of (|p|, |grad*grad_scale|, |grad*grad_scale + wd*p|) per table row (the
+        parameters in order, then the EMA-only rows, which stay 0) that the last step's norm pass wrote; None when
+        neither LARS nor clipping is on.  Returned without synchronising: the global gradient norm is
+        ``last_norms()[:, 2].double().square().sum().sqrt()``, the trust ratios are ``last_lr_scale()``."""
+        return self._norms
+
+    def last_lr_scale(self):
+        """The device tensor [ntens] of per-tensor rate factors (LARS trust ratios; 1 where not adapted)."""
+        return self._lr_scale
+
+    def norm_stats(self):
+        """Host-side digest of the last step's norms (reads the device: call on logged steps, after their sync)."""
+        if self._norms is None:
+            return {}
+        n = self._norms.detach().cpu().double()
+        out = {"grad_norm": float(n[:, 2].square().sum().sqrt())}
+        adapted = [i for i, p in enumerate(self.params) if self.state[p]["adapt"]]
+        if self.kind == "lars" and adapted:
+            r = self._lr_scale.detach().cpu()[adapted]
+            out["lars/min_trust_ratio"], out["lars/max_trust_ratio"] = float(r.min()), float(r.max())
+        return out
 
     def step(self, lr=None, grad_scale=1.0, skip_flag=None):
         lr = self.lr if lr is None else lr
@@ -154,7 +248,31 @@ class FusedOptimizer:
         if skip_flag is not None and int(skip_flag.item()) != 0:
             return
         d = self.ema_decay_now()
-        for p in self.params:
+        gclip = 1.0
+        if self.scaled:  # the norm pass: fp32 terms as the kernel forms them, fp64 sums
+            self._norms.zero_()
+            self._lr_scale.fill_(1.0)
+            total = 0.0
+            for i, p in enumerate(self.params):
+                st = self.state[p]
+                g = getattr(p, "main_grad", None)
+                if g is None:
+                    g = p.grad
+                if g is None:
+                    continue
+                gs = g.float() * grad_scale
+                ge = g.float() * grad_scale + st["wd"] * p
+                pn = math.sqrt(float(p.detach().double().square().sum()))
+                gn = math.sqrt(float(gs.double().square().sum()))
+                ge2 = float(ge.double().square().sum())
+                total += ge2
+                self._norms[i, 0], self._norms[i, 1], self._norms[i, 2] = pn, gn, math.sqrt(ge2)
+                if st["adapt"] and pn > 0.0 and gn > 0.0:
+                    self._lr_scale[i] = self.lars_eeta * pn / (gn + st["wd"] * pn + self.lars_eps)
+            if self.clip > 0.0:
+                gclip = float(np.float32(self.clip / max(math.sqrt(total), self.clip)))
+            self._gclip.fill_(gclip)
+        for i, p in enumerate(self.params):
             st = self.state[p]
             g = getattr(p, "main_grad", None)
             if g is None:
@@ -162,10 +280,14 @@ class FusedOptimizer:
             if g is None:
                 continue
             g = g.float() * grad_scale + st["wd"] * p
+            if self.clip > 0.0:
+                g = g * gclip
             lr_p = lr * st["lr_mult"]
+            if self.kind == "lars":
+                lr_p = lr_p * float(self._lr_scale[i])
             if self.kind == "sgd":
                 p.sub_(lr_p * g)
-            elif self.kind == "momentum":
+            elif self.kind in ("momentum", "lars"):
                 st["s1"].mul_(self.mu).add_(g)
                 p.sub_(lr_p * st["s1"])
             else:
@@ -184,14 +306,16 @@ class FusedOptimizer:
     # ---- state for checkpoints (TF slot names) -------------------------------------------------
     def slot_variables(self):
         """(tf_name, tensor) for optimizer slots: Momentum -> <v>/Momentum, RMSProp -> <v>/RMSProp (ms),
-        <v>/RMSProp_1 (mom), EMA -> <v>/ExponentialMovingAverage."""
+        <v>/RMSProp_1 (mom), EMA -> <v>/ExponentialMovingAverage.  LARS saves its accumulator as <v>/Momentum too,
+        so momentum and LARS runs resume into each other; the slot name TensorFlow's own contrib LARS optimizer
+        writes is not checked here (TensorFlow is not part of the test environment)."""
         out = []
         for p in self.params:
             name = getattr(p, "tf_name", None)
             if name is None:
                 continue
             st = self.state[p]
-            if self.kind == "momentum":
+            if self.kind in ("momentum", "lars"):
                 out.append((name + "/Momentum", st["s1"]))
             elif self.kind == "rmsprop":
                 out.append((name + "/RMSProp", st["s2"]))

@@ -20,7 +20,7 @@ import torch
 
 from .ckpt.saver import Saver, TFVar, model_variables
 from .compat import logging
-from .compat.train import ExponentialDecay, Server
+from .compat.train import ExponentialDecay, LinearWarmup, PolynomialDecay, Server
 from .engine import TrainStep
 from .models import nets_factory
 from .parallel import process_group as pg
@@ -104,6 +104,10 @@ PRESETS = {
 }
 
 
+LARGE_BATCH_BSP_ONLY = ("--optimizer lars and --clip_global_norm need --sync_mode bsp (got %s): under asp / ssp the "
+                        "update runs on owner shards from one worker's push, where no global gradient norm exists")
+
+
 def define_common_flags(flags, preset):
     """Flags shared by every trainer (reference flag inventory) + MI355X extras."""
     p = PRESETS[preset]
@@ -134,6 +138,16 @@ def define_common_flags(flags, preset):
             ("initial_learning_rate", Fl, p["lr"], "Initial learning rate."),
             ("num_epochs_per_decay", Fl, p["decay_epochs"], "Epochs after which learning rate decays."),
             ("learning_rate_decay_factor", Fl, p["decay_factor"], "Learning rate decay factor."),
+            # large-batch training (all default to the preset's behaviour)
+            ("optimizer", S, "", "sgd | momentum | rmsprop | lars (default: the preset's optimizer); lars is BSP only"),
+            ("lars_eeta", Fl, 0.001, "LARS trust coefficient"),
+            ("lars_epsilon", Fl, 0.0, "LARS epsilon in the trust ratio's denominator"),
+            ("clip_global_norm", Fl, 0.0, "clip the gradient by this global norm (0 = off); BSP only, not with lars"),
+            ("warmup_steps", I, 0, "linear learning-rate warm-up from 0 over the first N steps (0 = off)"),
+            ("lr_decay", S, "", "exponential (the preset's staircase decay, the default) | polynomial (from "
+             "--initial_learning_rate to --end_learning_rate over --max_steps steps)"),
+            ("end_learning_rate", Fl, 0.0001, "polynomial decay: the final learning rate"),
+            ("lr_power", Fl, 1.0, "polynomial decay: the power"),
             # MI355X-native extras
             ("sync_mode", S, "", "bsp | asp | ssp (default from the entry script)"),
             ("max_staleness", I, 5, "SSP staleness bound in local steps"),
@@ -228,6 +242,14 @@ def train(preset, flags, default_mode="bsp"):
     cfg = dict(PRESETS[preset])
     mode = (FLAGS.sync_mode or default_mode).lower()
     logging.set_verbosity(logging.INFO)
+    optimizer = (FLAGS.optimizer or cfg["optimizer"]).lower()
+    if optimizer not in ("sgd", "momentum", "rmsprop", "lars"):
+        raise ValueError("--optimizer must be sgd, momentum, rmsprop or lars, got %r" % FLAGS.optimizer)
+    if FLAGS.lr_decay not in ("", "exponential", "polynomial"):
+        raise ValueError("--lr_decay must be exponential or polynomial, got %r" % FLAGS.lr_decay)
+    if mode in ("asp", "ssp") and (optimizer == "lars" or FLAGS.clip_global_norm > 0):
+        # checked before any process group or store exists: every rank fails at once
+        raise ValueError(LARGE_BATCH_BSP_ONLY % mode)
     ps_hosts = [h for h in FLAGS.ps_hosts.split(",") if h]
     worker_hosts = [h for h in FLAGS.worker_hosts.split(",") if h]
     if FLAGS.job_name == "ps":
@@ -277,7 +299,12 @@ def train(preset, flags, default_mode="bsp"):
     scale = world if (cfg["lr_scale_workers"] and mode == "bsp") else 1
     sched = ExponentialDecay(FLAGS.initial_learning_rate * scale, max(decay_steps, 1.0),
                              FLAGS.learning_rate_decay_factor, staircase=True)
-    opt_kw = dict(optimizer=cfg["optimizer"], lr=sched(0), momentum=cfg.get("momentum", 0.9),
+    if FLAGS.lr_decay == "polynomial":
+        sched = PolynomialDecay(FLAGS.initial_learning_rate * scale, max(FLAGS.max_steps, 1), FLAGS.end_learning_rate,
+                                FLAGS.lr_power)
+    if FLAGS.warmup_steps > 0:
+        sched = LinearWarmup(sched, FLAGS.warmup_steps)
+    opt_kw = dict(optimizer=optimizer, lr=sched(0), momentum=cfg.get("momentum", 0.9),
                   rho=cfg.get("rmsprop_decay", 0.9), epsilon=cfg.get("rmsprop_epsilon", 1e-10))
 
     # ---- engine + supervisor / checkpoints (C7, §5.4) -------------------------------------------
@@ -312,7 +339,9 @@ def train(preset, flags, default_mode="bsp"):
                             wgrad_stream=cfg.get("wgrad_stream"),
                             grad_comm_dtype=torch.bfloat16 if FLAGS.grad_comm_dtype == "bf16" else None,
                             timer=StepTimer() if (FLAGS.metrics_file and rank == 0 and not FLAGS.use_hipgraph)
-                            else None, **opt_kw)
+                            else None, lars_eeta=FLAGS.lars_eeta, lars_epsilon=FLAGS.lars_epsilon,
+                            clip_global_norm=FLAGS.clip_global_norm if FLAGS.clip_global_norm > 0 else None,
+                            **opt_kw)
         vars_ = model_variables(model, step_fn.opt, gstep, **ckpt_kw)
         vars_[-1].name = cfg.get("global_step_name", "global_step")
         if path:
@@ -334,7 +363,7 @@ def train(preset, flags, default_mode="bsp"):
         if path:  # owners initialise their shards from the restored replica
             Saver(vars_).restore(path)
         prepare_compute_copies(model)
-        store = ParamStore(list(model.parameters()), cfg["optimizer"], sched(0), opt_kw["momentum"], opt_kw["rho"],
+        store = ParamStore(list(model.parameters()), optimizer, sched(0), opt_kw["momentum"], opt_kw["rho"],
                            opt_kw["epsilon"], run_id=os.environ.get("DTM_RUN_ID", "0"),
                            buffers=moving_average_buffers(model))
         if is_chief and int(gstep):
@@ -455,6 +484,16 @@ def train(preset, flags, default_mode="bsp"):
             if summ is not None and summ_now:
                 summ.write(tbw, gs)
             extra = step_fn.timer.sections() if (mode == "bsp" and step_fn.timer is not None) else {}
+            if mode == "bsp" and step_fn.opt.scaled and (metrics.f is not None or (tbw is not None and summ_now)):
+                # the norm pass's results of this step (LARS / clipping only), read after the logged step's
+                # synchronisation above: no other step reads them on the host
+                ns = step_fn.opt.norm_stats()
+                if math.isfinite(ns["grad_norm"]) and tbw is not None and summ_now:
+                    tbw.add_scalar("gradient_norm", ns["grad_norm"], gs)
+                    for k in ("lars/min_trust_ratio", "lars/max_trust_ratio"):
+                        if k in ns:
+                            tbw.add_scalar(k, ns[k], gs)
+                extra.update(ns)
             if mode == "bsp" and metrics.f is not None and world > 1:
                 bms = step_fn.dp.bucket_ms()  # per-bucket all-reduce durations (RCCL timing events)
                 if bms:

@@ -10,6 +10,7 @@
 //   Momentum       a = mu*a + g;  p -= lr*a            (use_nesterov=False)
 //   RMSProp (TF)   ms = rho*ms + (1-rho)*g^2;  mom = mu*mom + lr*g/sqrt(ms+eps);  p -= mom
 //   LARS           the Momentum update with the rate lr*lr_scale[t] (trust ratio from the norm pass below)
+//   Adam           its own entry point and kernel (dtm_multi_tensor_adam, below the norm pass)
 // with g = grad*grad_scale + wd*p (coupled L2, the gradient of wd*sum(p^2)/2), optionally times the
 // clip-by-global-norm factor of the norm pass, an optional
 // fused ExponentialMovingAverage shadow update (decay already min'd with (1+n)/(10+n) on the
@@ -264,6 +265,131 @@ __global__ __launch_bounds__(NORM_FIN_THREADS) void multi_tensor_norm_finalize_k
   }
 }
 
+// ---- Adam (TF 1.x AdamOptimizer: no Nesterov, no AMSGrad) ---------------------------------------------------------
+//   m = b1*m + (1-b1)*g;  v = b2*v + (1-b2)*g*g;  p -= lr*lr_mult * sqrt(1-b2^t)/(1-b1^t) * m / (sqrt(v) + eps)
+// over the same OptTensor rows (s1 = m, s2 = v) and OptChunk list, g as above.  t is the number of APPLIED updates:
+// the NaN guard skips an update on the device without the host knowing, and the step may be a replayed hipGraph, so
+// t and the two correction terms live in a 16-byte device record that a one-thread launch in front of the update
+// advances (stream order is the only synchronisation; nothing but the record's contents changes between replays).
+struct AdamState {
+  int t;      // applied updates so far
+  float bc1;  // 1 - b1^t        } from t in fp64, rounded once
+  float bc2;  // sqrt(1 - b2^t)  }
+  int pad;
+};
+struct AdamHyper {
+  float b1, omb1, b2, omb2, eps;  // omb = 1 - b, rounded from the fp64 difference (1 - 0.999f is 1.3e-5 off 0.001)
+  int use_ema;
+  const int* skip_flag;
+  const float* dyn;    // device scalars [lr, ema_decay, grad_scale]
+  const float* gclip;  // optional clip-by-global-norm factor of the norm pass
+  const AdamState* state;
+};
+
+__global__ void adam_advance_kernel(AdamState* st, const int* skip_flag, double b1, double b2) {
+  if (skip_flag && *skip_flag) return;
+  const int t = st->t + 1;
+  double p1 = 1.0, p2 = 1.0, q1 = b1, q2 = b2;  // b^t by squaring: no product carried from step to step
+  for (int e = t; e > 0; e >>= 1) {
+    if (e & 1) { p1 *= q1; p2 *= q2; }
+    q1 *= q1; q2 *= q2;
+  }
+  st->t = t;
+  st->bc1 = (float)(1.0 - p1);
+  st->bc2 = (float)sqrt(1.0 - p2);
+}
+
+// One element.  Every operation is spelled out (no contraction left to the compiler), so the 16-byte and the 4-byte
+// path of the kernel below give the same bits for the same element.
+__device__ __forceinline__ void adam_elem(float& p, float graw, float& m, float& v, float wd, float grad_scale,
+                                          bool clip, float gclip, float alpha, const AdamHyper& h) {
+  float g = __fmaf_rn(graw, grad_scale, __fmul_rn(wd, p));
+  if (clip) g = __fmul_rn(g, gclip);
+  m = __fmaf_rn(h.b1, m, __fmul_rn(h.omb1, g));
+  v = __fmaf_rn(h.b2, v, __fmul_rn(__fmul_rn(h.omb2, g), g));
+  p = __fmaf_rn(-alpha, __fdiv_rn(m, __fadd_rn(__fsqrt_rn(v), h.eps)), p);
+}
+__device__ __forceinline__ float ema_elem(float e, float p, float omd) {  // e -= (1-d)(e - p)
+  return __fmaf_rn(-omd, __fsub_rn(e, p), e);
+}
+
+// 30 B per element (+2 B bf16 copy, +8 B EMA): 16-byte accesses where weight, gradient, m, v (and the shadow; the
+// bf16 copy at 8 bytes) reach a 16-byte boundary together, with a scalar head and tail, as the norm pass does;
+// coalesced 4-byte accesses otherwise (gradients are views into the flat bucket buffer at any element offset).
+__global__ __launch_bounds__(256) void multi_tensor_adam_kernel(const OptTensor* __restrict__ tens,
+                                                                const OptChunk* __restrict__ chunks, AdamHyper h) {
+  if (h.skip_flag && *h.skip_flag) return;
+  const int tid = threadIdx.x;
+  const OptChunk c = chunks[blockIdx.x];
+  const OptTensor t = tens[c.t];
+  const long rem = t.n - c.start;
+  const int len = (int)(rem < (long)OPT_CHUNK ? (rem > 0 ? rem : 0) : (long)OPT_CHUNK);
+  const float ema_decay = h.dyn[1], grad_scale = h.dyn[2];
+  if (!t.g) {  // EMA-only row (BN moving statistics), as in multi_tensor_opt_kernel
+    if (h.use_ema && t.ema) {
+      const float* bp = t.p + c.start;
+      float* sp = t.ema + c.start;
+      for (int i = tid; i < len; i += 256) sp[i] -= (1.f - ema_decay) * (sp[i] - bp[i]);
+    }
+    return;
+  }
+  const AdamState s = *h.state;
+  const float alpha = __fdiv_rn(__fmul_rn(__fmul_rn(h.dyn[0], t.lr_mult), s.bc2), s.bc1);
+  const float omd = 1.f - ema_decay;
+  const bool clip = h.gclip != nullptr;
+  const float gclip = clip ? h.gclip[0] : 1.f;
+  float* pp = t.p + c.start;
+  const float* gp = t.g + c.start;
+  float* mp = t.s1 + c.start;
+  float* vp = t.s2 + c.start;
+  float* ep = (h.use_ema && t.ema) ? t.ema + c.start : nullptr;
+  bf16_t* cp = t.pcopy ? t.pcopy + c.start : nullptr;
+
+  auto scalar = [&](int i) {
+    float p = pp[i], m = mp[i], v = vp[i];
+    adam_elem(p, gp[i], m, v, t.wd, grad_scale, clip, gclip, alpha, h);
+    pp[i] = p; mp[i] = m; vp[i] = v;
+    if (cp) cp[i] = f2bf(p);
+    if (ep) ep[i] = ema_elem(ep[i], p, omd);
+  };
+
+  const uintptr_t pa = (uintptr_t)pp;
+  uintptr_t off = (pa ^ (uintptr_t)gp) | (pa ^ (uintptr_t)mp) | (pa ^ (uintptr_t)vp);
+  if (ep) off |= pa ^ (uintptr_t)ep;
+  const int head16 = (int)(((16u - (unsigned)(pa & 15u)) & 15u) >> 2);  // elements up to the 16-byte boundary
+  if ((off & 15u) == 0 && (!cp || ((uintptr_t)(cp + head16) & 7u) == 0)) {
+    const int head = head16 < len ? head16 : len;
+    const int nvec = (len - head) >> 2, tail0 = head + (nvec << 2);
+    if (tid < head) scalar(tid);
+    f32x4* pv = (f32x4*)(pp + head);
+    const f32x4* gv = (const f32x4*)(gp + head);
+    f32x4* mv = (f32x4*)(mp + head);
+    f32x4* vv = (f32x4*)(vp + head);
+    for (int i = tid; i < nvec; i += 256) {
+      f32x4 pw = pv[i], mw = mv[i], vw = vv[i];
+      const f32x4 gw = gv[i];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float p = pw[e], m = mw[e], v = vw[e];
+        adam_elem(p, gw[e], m, v, t.wd, grad_scale, clip, gclip, alpha, h);
+        pw[e] = p; mw[e] = m; vw[e] = v;
+      }
+      pv[i] = pw; mv[i] = mw; vv[i] = vw;
+      if (cp) ((uint2*)(cp + head))[i] = make_uint2(pack2bf(pw[0], pw[1]), pack2bf(pw[2], pw[3]));
+      if (ep) {
+        f32x4* ev = (f32x4*)(ep + head);
+        f32x4 ew = ev[i];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) ew[e] = ema_elem(ew[e], pw[e], omd);
+        ev[i] = ew;
+      }
+    }
+    if (tail0 + tid < len) scalar(tail0 + tid);
+  } else {
+    for (int i = tid; i < len; i += 256) scalar(i);
+  }
+}
+
 __global__ void check_finite_kernel(const float* __restrict__ x, long n, int* __restrict__ flag) {
   bool bad = false;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
@@ -381,6 +507,28 @@ DTM_API void dtm_multi_tensor_opt(const void* tensors_dev, const void* chunks_de
                                   const int* skip_flag, const float* dyn, void* stream) {
   dtm_multi_tensor_opt_scaled(tensors_dev, chunks_dev, num_chunks, kind, lr, mu, rho, eps, grad_scale, ema_decay,
                               use_ema, skip_flag, dyn, nullptr, nullptr, stream);
+}
+
+DTM_API int dtm_adam_state_bytes() { return (int)sizeof(AdamState); }
+
+// The Adam step over the optimizer's tables (as dtm_multi_tensor_opt; s1 = m, s2 = v): a one-thread launch advances
+// the device record ``state`` (AdamState, zeroed by the owner before the first step) unless *skip_flag, then the
+// update reads it.  dyn: device scalars [lr, ema_decay, grad_scale]; gclip: the norm pass's clip factor or null.
+// Nothing is allocated, uploaded or read back: the two launches can be captured into a hipGraph.
+DTM_API int dtm_multi_tensor_adam(const void* tensors_dev, const void* chunks_dev, int num_chunks, double b1,
+                                  double b2, double eps, int use_ema, const int* skip_flag, const float* dyn,
+                                  const float* gclip, void* state, void* stream) {
+  if (num_chunks < 0 || !dyn || !state || !(b1 >= 0.0 && b1 < 1.0) || !(b2 >= 0.0 && b2 < 1.0)) return -1;
+  if (num_chunks > 0 && (!tensors_dev || !chunks_dev)) return -1;
+  AdamHyper h;
+  h.b1 = (float)b1; h.omb1 = (float)(1.0 - b1); h.b2 = (float)b2; h.omb2 = (float)(1.0 - b2); h.eps = (float)eps;
+  h.use_ema = use_ema; h.skip_flag = skip_flag; h.dyn = dyn; h.gclip = gclip; h.state = (const AdamState*)state;
+  hipLaunchKernelGGL(adam_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (AdamState*)state, skip_flag, b1,
+                     b2);
+  if (num_chunks > 0)
+    hipLaunchKernelGGL(multi_tensor_adam_kernel, dim3(num_chunks), dim3(256), 0, (hipStream_t)stream,
+                       (const OptTensor*)tensors_dev, (const OptChunk*)chunks_dev, h);
+  return 0;
 }
 
 DTM_API int dtm_opt_norm_meta_bytes() { return (int)sizeof(NormMeta); }

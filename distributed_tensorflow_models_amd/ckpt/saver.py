@@ -6,7 +6,9 @@
 * TF variable names and layouts: conv kernels are exported HWIO ([R,S,C,K]) from the internal
   [K,R,S,C]; optimizer slots ``<v>/Momentum`` (momentum, and LARS: the two resume into each other; the slot name
   of TensorFlow's own contrib LARS optimizer is not checked here, TensorFlow is not part of the test environment),
-  ``<v>/RMSProp``, ``<v>/RMSProp_1``; EMA shadows
+  ``<v>/RMSProp``, ``<v>/RMSProp_1``; Adam ``<v>/Adam`` (m), ``<v>/Adam_1`` (v) and the scalars ``beta1_power``,
+  ``beta2_power`` = b^(t+1) after t applied updates, from which a restore recovers t (parity of these names with a
+  file written by TensorFlow itself is not checked either); EMA shadows
   ``<v>/ExponentialMovingAverage``; ``global_step`` int64;
 * ``max_to_keep`` retention; writes are atomic (tempstate + rename in the native writer);
 * the ``.meta`` GraphDef is not produced (there is no TF graph) - documented deviation.
@@ -56,6 +58,29 @@ class TFVar:
             self.tensor.copy_(t.to(self.tensor.dtype))
 
 
+class AdamPowerVar(TFVar):
+    """``beta1_power`` / ``beta2_power`` of an Adam optimizer: b^(t+1) in fp32 after t applied updates (TensorFlow's
+    variables start at b).  The value is formed from the optimizer's applied-update count when the variable is saved
+    (``refresh``: reads the device) and handed back to the optimizer on load, where ``FusedOptimizer.restored``
+    recovers t from it."""
+    __slots__ = ("optimizer", "which")
+
+    def __init__(self, name, optimizer, which):
+        TFVar.__init__(self, name, torch.zeros((), dtype=torch.float32))
+        self.optimizer, self.which = optimizer, which
+
+    def refresh(self):
+        self.tensor.fill_(float(self.optimizer.beta_powers()[self.which]))
+
+    def export(self):
+        self.refresh()
+        return TFVar.export(self)
+
+    def load(self, arr):
+        TFVar.load(self, arr)
+        self.optimizer._adam_loaded["beta%d_power" % (self.which + 1)] = float(self.tensor)
+
+
 def model_variables(model, optimizer=None, global_step=None, include_slots=True, prefix="", partitions=None,
                     store=None):
     """Collect TFVar records for a model built from models.layers (+ optimizer slots / EMA).
@@ -81,12 +106,18 @@ def model_variables(model, optimizer=None, global_step=None, include_slots=True,
             elif optimizer.kind == "rmsprop":
                 out.append(TFVar(base.name + "/RMSProp", st["s2"], base.layout, partitions))
                 out.append(TFVar(base.name + "/RMSProp_1", st["s1"], base.layout, partitions))
+            elif optimizer.kind == "adam":
+                out.append(TFVar(base.name + "/Adam", st["s1"], base.layout, partitions))
+                out.append(TFVar(base.name + "/Adam_1", st["s2"], base.layout, partitions))
             if "ema" in st:
                 out.append(TFVar(base.name + "/ExponentialMovingAverage", st["ema"], base.layout, partitions))
         for b, shadow in getattr(optimizer, "buffer_shadows", lambda: [])():
             base = by_param.get(id(b))
             if base is not None:
                 out.append(TFVar(base.name + "/ExponentialMovingAverage", shadow, base.layout, partitions))
+        if optimizer.kind == "adam":
+            out.append(AdamPowerVar(prefix + "beta1_power", optimizer, 0))
+            out.append(AdamPowerVar(prefix + "beta2_power", optimizer, 1))
     if store is not None and include_slots:
         # ASP / SSP: the slots live in the owner shards (every rank maps every shard)
         for i, p in enumerate(store.params):
@@ -186,6 +217,8 @@ class Saver:
         on the current stream; returns (arrays-producer, event)."""
         host = []
         for v in self.vars:
+            if isinstance(v, AdamPowerVar):
+                v.refresh()
             t = v.tensor.detach()
             if v.layout == "KRSC->HWIO":
                 t = t.permute(1, 2, 3, 0)

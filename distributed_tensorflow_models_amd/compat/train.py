@@ -243,6 +243,15 @@ class RMSPropOptimizer(Optimizer):
         super().__init__(learning_rate, rho=decay, momentum=momentum, epsilon=epsilon)
 
 
+class AdamOptimizer(Optimizer):
+    """tf.train.AdamOptimizer (ops/optim.py: the bias correction counts the updates actually applied, on the
+    device).  BSP / single-worker only."""
+    kind = "adam"
+
+    def __init__(self, learning_rate=0.001, beta1=0.9, beta2=0.999, epsilon=1e-8):
+        super().__init__(learning_rate, beta1=beta1, beta2=beta2, epsilon=epsilon)
+
+
 class SyncReplicasOptimizer:
     """BSP wrapper: gradients of all replicas are averaged before one update (C9).  With
     replicas_to_aggregate == total_num_replicas (every reference call site) this is exactly a
@@ -449,6 +458,9 @@ class TrainOp:
             raise ValueError("LARSOptimizer and clip_global_norm need the BSP step (SyncReplicasOptimizer or one "
                              "worker): under ASP the update runs on owner shards from one worker's push, where no "
                              "global gradient norm exists")
+        if base.kind == "adam" and self.mode != "bsp":
+            raise ValueError("AdamOptimizer needs the BSP step (SyncReplicasOptimizer or one worker): the owner "
+                             "shards of ASP keep no shared count of applied updates for the bias correction")
         if weight_decay is None:
             weight_decay = getattr(base, "weight_decay", None)
         if weight_decay is not None:
@@ -467,7 +479,8 @@ class TrainOp:
                                   ema_decay=ema.decay if ema is not None else None, ema_buffers=ema_buffers,
                                   momentum=kw.get("momentum", 0.9), rho=kw.get("rho", 0.9),
                                   epsilon=kw.get("epsilon", 1e-10), lars_eeta=kw.get("lars_eeta", 0.001),
-                                  lars_epsilon=kw.get("lars_epsilon", 0.0), clip_global_norm=clip_global_norm)
+                                  lars_epsilon=kw.get("lars_epsilon", 0.0), clip_global_norm=clip_global_norm,
+                                  beta1=kw.get("beta1", 0.9), beta2=kw.get("beta2", 0.999))
             self.step.loss_fn = self._loss
             self.store = None
         else:
@@ -532,7 +545,7 @@ class TrainOp:
         invalidate_weight_copies(self.model.parameters())
         if self.mode == "bsp" and self.global_step is not None:
             self.step.global_step = int(self.global_step)
-            self.step.opt.num_updates = int(self.global_step)
+            self.step.opt.restored(int(self.global_step))
 
 
 class Saver:

@@ -105,12 +105,13 @@ RESERVED_CUS_DP = 0
 
 
 class TrainStep:
-    def __init__(self, model, optimizer="momentum", lr=0.1, momentum=0.9, rho=0.9, epsilon=1e-10, bucket_mb=32.0,
+    def __init__(self, model, optimizer="momentum", lr=0.1, momentum=0.9, rho=0.9, epsilon=None, bucket_mb=32.0,
                  label_smoothing=0.0, aux_weight=0.4, ema_decay=None, lr_schedule=None, use_graph=False,
                  process_group=None, weight_decay=None, batch_weight=1.0, nan_guard=True, timer=None,
                  grad_comm_dtype=None, ema_buffers=True, bn_sync_every=1, wgrad_stream=None, bsp_check=None,
                  overlap=True, force_comm=False, graph_comm=False, lars_eeta=0.001, lars_epsilon=0.0,
-                 clip_global_norm=None):
+                 clip_global_norm=None, beta1=0.9, beta2=0.999):
+        # epsilon None: the optimizer's own default (1e-10; Adam 1e-8); beta1 / beta2: Adam only
         self.model = model
         if wgrad_stream is not None:
             # conv+BN weight gradients on the side stream (ops/_lib.py side_stream; process-wide): ResNet-50
@@ -140,7 +141,8 @@ class TrainStep:
         self.opt = FusedOptimizer(params, optimizer, lr, momentum, rho, epsilon, ema_decay, weight_decay,
                                   ema_buffers=moving_average_buffers(model)
                                   if (ema_decay is not None and ema_buffers) else (),
-                                  lars_eeta=lars_eeta, lars_epsilon=lars_epsilon, clip_global_norm=clip_global_norm)
+                                  lars_eeta=lars_eeta, lars_epsilon=lars_epsilon, clip_global_norm=clip_global_norm,
+                                  beta1=beta1, beta2=beta2)
         self.lr = lr
         self.lr_schedule = lr_schedule
         self.smoothing = label_smoothing

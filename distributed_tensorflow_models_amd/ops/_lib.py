@@ -30,6 +30,7 @@ _P = ctypes.c_void_p
 _I = ctypes.c_int
 _L = ctypes.c_long
 _F = ctypes.c_float
+_D = ctypes.c_double
 
 _SIGS = {
     "dtm_conv_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, ctypes.POINTER(ConvDesc), _P]),
@@ -109,6 +110,8 @@ _SIGS = {
     "dtm_opt_norm_meta_bytes": (_I, []),
     "dtm_opt_norm_scratch_bytes": (_L, [_I, _I]),
     "dtm_multi_tensor_norms": (_I, [_P, _P, _I, _P, _I, _P, _F, _F, _F, _F, _P, _P, _P, _P, _P]),
+    "dtm_adam_state_bytes": (_I, []),
+    "dtm_multi_tensor_adam": (_I, [_P, _P, _I, _D, _D, _D, _I, _P, _P, _P, _P, _P]),
     "dtm_check_finite": (None, [_P, _L, _P, _P]),
     "dtm_f32_to_bf16": (None, [_P, _P, _L, _P]),
     "dtm_scale": (None, [_P, _L, _F, _P]),

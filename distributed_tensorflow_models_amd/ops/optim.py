@@ -10,6 +10,13 @@ TF 1.x update semantics:
                             lr_scale[t] = eeta*|p| / (|gs| + wd_t*|p| + eps)  for an adapted tensor with |p| > 0
                             and |gs| > 0 (gs = grad*grad_scale), 1 otherwise; tensors with ndim <= 1 (biases, BN
                             beta / gamma) are not adapted
+  AdamOptimizer             m = b1*m + (1-b1)*g; v = b2*v + (1-b2)*g*g;
+                            p -= lr * sqrt(1-b2^t)/(1-b1^t) * m / (sqrt(v) + eps)
+                            (eps outside the root and not bias-corrected; no Nesterov, no AMSGrad; m, v start at 0).
+                            t = the number of updates actually APPLIED, this one included: an update that the NaN
+                            guard skips on the device does not count, so t lives in a small device record that a
+                            one-thread launch advances in front of the update (also inside a replayed hipGraph); the
+                            host reads it only in ``adam_step()``.  Weight decay stays the coupled L2 term (no AdamW).
   g = grad*grad_scale + weight_decay*p   (coupled L2 = d/dp of wd*sum(p^2)/2; K14)
   clip_global_norm (tf.clip_by_global_norm): g *= clip / max(sqrt(sum over all tensors of |g|^2), clip); the L2
                             term is part of g because the reference puts it in the loss
@@ -29,16 +36,33 @@ import torch
 
 from . import _lib
 
-# kernel update rule per kind (LARS is the momentum rule with a per-tensor rate factor)
-KINDS = {"sgd": 0, "momentum": 1, "rmsprop": 2, "lars": 1}
+# kernel update rule per kind (LARS is the momentum rule with a per-tensor rate factor; Adam has its own entry point)
+KINDS = {"sgd": 0, "momentum": 1, "rmsprop": 2, "lars": 1, "adam": 3}
+
+
+def _bias_corrections(b1, b2, t):
+    """(1 - b1^t, sqrt(1 - b2^t)) from t in fp64, rounded once to fp32: what the device record holds."""
+    return np.float32(1.0 - b1 ** t), np.float32(math.sqrt(1.0 - b2 ** t))
+
+
+def _slot_like(p, fill=0.0):
+    """An fp32 slot for ``p`` that sits at p's own offset from a 16-byte boundary, so that the Adam kernel's 16-byte
+    path depends on the weight and its gradient alone (a fresh allocation is aligned; a weight that is a view may not
+    be)."""
+    off = (p.data_ptr() % 16) // 4 if p.is_cuda else 0
+    if off == 0:
+        return torch.full_like(p, fill, dtype=torch.float32)
+    buf = torch.full((p.numel() + off,), fill, dtype=torch.float32, device=p.device)
+    return buf[off:].view(p.shape)
 
 
 class FusedOptimizer:
-    def __init__(self, params, kind="momentum", lr=0.1, momentum=0.9, rho=0.9, epsilon=1e-10, ema_decay=None,
+    def __init__(self, params, kind="momentum", lr=0.1, momentum=0.9, rho=0.9, epsilon=None, ema_decay=None,
                  weight_decay=None, lr_mults=None, ema_buffers=(), lars_eeta=0.001, lars_epsilon=0.0,
-                 clip_global_norm=None, lars_skip=None):
+                 clip_global_norm=None, lars_skip=None, beta1=0.9, beta2=0.999):
         """``lars_skip``: predicate on a parameter, True = its rate is not adapted (default: ``p.ndim <= 1``).
-        ``clip_global_norm``: threshold of the clip by global norm (None or 0: off); not combined with LARS."""
+        ``clip_global_norm``: threshold of the clip by global norm (None or 0: off); not combined with LARS.
+        ``epsilon``: None = 1e-10 (RMSProp's) or, for Adam, 1e-8.  ``beta1`` / ``beta2``: Adam only."""
         self.params = [p for p in params if p.requires_grad]
         # non-trainable tensors that also get an EMA shadow (BN moving mean/variance: the reference
         # averages trainable_variables() + moving_average_variables(), e.g. reference
@@ -52,7 +76,12 @@ class FusedOptimizer:
             raise ValueError("clip_global_norm must be positive, got %r" % (clip_global_norm,))
         if kind == "lars" and clip > 0.0:
             raise ValueError("LARS and clip_global_norm are not combined (the order of the two is not defined)")
+        if epsilon is None:
+            epsilon = 1e-8 if kind == "adam" else 1e-10
         self.kind, self.lr, self.mu, self.rho, self.eps = kind, lr, momentum, rho, epsilon
+        self.b1, self.b2 = float(beta1), float(beta2)
+        if kind == "adam" and not (0.0 <= self.b1 < 1.0 and 0.0 <= self.b2 < 1.0):
+            raise ValueError("beta1 and beta2 must be in [0, 1), got %r, %r" % (beta1, beta2))
         self.lars_eeta, self.lars_eps, self.clip = float(lars_eeta), float(lars_epsilon), clip
         self.scaled = kind == "lars" or clip > 0.0  # the step needs the norm pass
         if lars_skip is None:
@@ -66,14 +95,19 @@ class FusedOptimizer:
                 st["s1"] = torch.zeros_like(p, dtype=torch.float32)
             if kind == "rmsprop":
                 st["s2"] = torch.ones_like(p, dtype=torch.float32)  # TF RMSProp ms slot init 1.0
+            if kind == "adam":
+                st["s1"], st["s2"] = _slot_like(p), _slot_like(p)  # m, v
             if ema_decay is not None:
-                st["ema"] = p.detach().clone().float()
+                st["ema"] = _slot_like(p).copy_(p.detach()) if kind == "adam" else p.detach().clone().float()
             st["wd"] = float(getattr(p, "weight_decay", 0.0) if weight_decay is None else weight_decay)
             st["lr_mult"] = 1.0 if lr_mults is None else float(lr_mults.get(p, 1.0))
             st["adapt"] = kind == "lars" and not lars_skip(p)
             self.state[p] = st
         self._dev = None
         self._norms = self._lr_scale = self._gclip = None
+        self._adam_t = 0          # CPU path: applied updates (the device path keeps them in _adam_state)
+        self._adam_state = None   # device record {int32 t, fp32 1-b1^t, fp32 sqrt(1-b2^t), pad}
+        self._adam_loaded = {}    # beta*_power values a checkpoint restore delivered (restored())
         if self.scaled and not (self.params and self.params[0].is_cuda):
             n = len(self.params) + len(self.ema_buffers)
             self._norms = torch.zeros((n, 3), dtype=torch.float32)
@@ -143,6 +177,9 @@ class FusedOptimizer:
             self._norms = torch.zeros((ntens, 3), dtype=torch.float32, device=dev)
             self._lr_scale = torch.ones(ntens, dtype=torch.float32, device=dev)
             self._gclip = torch.ones(1, dtype=torch.float32, device=dev)
+        if self.kind == "adam":
+            assert L.dtm_adam_state_bytes() == 16
+            self._adam_state = torch.zeros(4, dtype=torch.int32, device=dev)
         self._dyn = torch.zeros(3, dtype=torch.float32, device=dev)
         # ring of pinned staging rows: the host runs ahead of the GPU, so a row is reused only
         # after the copy that last read it has executed (its event), never overwritten in flight
@@ -184,6 +221,18 @@ class FusedOptimizer:
     def launch(self, skip_flag=None):
         """Issue the fused update reading lr/ema/grad_scale from the device scalars."""
         L = _lib.lib()
+        if self.kind == "adam":
+            # norm pass when clipping, then the state advance and the update (both inside the entry point)
+            if self.scaled:
+                self.launch_norms()
+            rc = L.dtm_multi_tensor_adam(_lib.ptr(self._tens_dev), _lib.ptr(self._chunks_dev), self._nchunks,
+                                         self.b1, self.b2, float(self.eps), int(self.ema_decay is not None),
+                                         _lib.ptr(skip_flag), _lib.ptr(self._dyn),
+                                         _lib.ptr(self._gclip) if self.clip > 0.0 else None,
+                                         _lib.ptr(self._adam_state), _lib.stream_ptr())
+            if rc != 0:
+                raise RuntimeError("dtm_multi_tensor_adam failed (%d)" % rc)
+            return
         if not self.scaled:
             L.dtm_multi_tensor_opt(_lib.ptr(self._tens_dev), _lib.ptr(self._chunks_dev), self._nchunks,
                                    KINDS[self.kind], 0.0, float(self.mu), float(self.rho), float(self.eps), 1.0, 0.0,
@@ -232,6 +281,46 @@ class FusedOptimizer:
             out["lars/min_trust_ratio"], out["lars/max_trust_ratio"] = float(r.min()), float(r.max())
         return out
 
+    def adam_step(self):
+        """The number of Adam updates applied so far (skipped ones not counted).  Reads the device: call it on
+        logged steps and at checkpoints only."""
+        if self._adam_state is not None:
+            return int(self._adam_state[0].item())
+        return self._adam_t
+
+    def set_adam_step(self, t):
+        """Set the applied-update count (a restore); the correction terms follow from it."""
+        t = max(0, int(t))
+        self._adam_t = t
+        if self._adam_state is not None:
+            bc1, bc2 = _bias_corrections(self.b1, self.b2, t)
+            rec = np.zeros(4, dtype=np.int32)
+            rec[0] = t
+            rec[1:3] = np.array([bc1, bc2], dtype=np.float32).view(np.int32)
+            self._adam_state.copy_(torch.from_numpy(rec))
+
+    def beta_powers(self):
+        """(b1^(t+1), b2^(t+1)) in fp32: the values of TensorFlow's beta1_power / beta2_power variables after t
+        applies (they start at b1 and b2).  Reads the device."""
+        t = self.adam_step()
+        return np.float32(self.b1 ** (t + 1)), np.float32(self.b2 ** (t + 1))
+
+    def restored(self, global_step):
+        """After a checkpoint restore: ``num_updates`` follows ``global_step``; Adam's applied-update count is
+        recovered from the restored beta2_power (b2^(t+1)), from beta1_power when b2 is 0 or the entry was absent
+        (or has underflowed), and from ``global_step`` when neither is there."""
+        self.num_updates = int(global_step)
+        if self.kind != "adam":
+            return
+        t = None
+        for name, b in (("beta2_power", self.b2), ("beta1_power", self.b1)):
+            v = self._adam_loaded.get(name)
+            if v is not None and 0.0 < b < 1.0 and 1.1754944e-38 <= v <= b * (1.0 + 1e-6):  # a normal fp32 b^(t+1)
+                t = int(round(math.log(v) / math.log(b))) - 1
+                break
+        self._adam_loaded = {}
+        self.set_adam_step(int(global_step) if t is None else t)
+
     def step(self, lr=None, grad_scale=1.0, skip_flag=None):
         lr = self.lr if lr is None else lr
         if self._dev is not None:
@@ -249,6 +338,9 @@ class FusedOptimizer:
             return
         d = self.ema_decay_now()
         gclip = 1.0
+        if self.kind == "adam":  # applied updates only: the early return above leaves the count alone
+            self._adam_t += 1
+            bc1, bc2 = _bias_corrections(self.b1, self.b2, self._adam_t)
         if self.scaled:  # the norm pass: fp32 terms as the kernel forms them, fp64 sums
             self._norms.zero_()
             self._lr_scale.fill_(1.0)
@@ -285,7 +377,11 @@ class FusedOptimizer:
             lr_p = lr * st["lr_mult"]
             if self.kind == "lars":
                 lr_p = lr_p * float(self._lr_scale[i])
-            if self.kind == "sgd":
+            if self.kind == "adam":
+                st["s1"].mul_(self.b1).add_(g, alpha=1 - self.b1)
+                st["s2"].mul_(self.b2).addcmul_(g, g, value=1 - self.b2)
+                p.sub_(float(np.float32(lr_p) * bc2 / bc1) * st["s1"] / (torch.sqrt(st["s2"]) + self.eps))
+            elif self.kind == "sgd":
                 p.sub_(lr_p * g)
             elif self.kind in ("momentum", "lars"):
                 st["s1"].mul_(self.mu).add_(g)
@@ -308,7 +404,9 @@ class FusedOptimizer:
         """(tf_name, tensor) for optimizer slots: Momentum -> <v>/Momentum, RMSProp -> <v>/RMSProp (ms),
         <v>/RMSProp_1 (mom), EMA -> <v>/ExponentialMovingAverage.  LARS saves its accumulator as <v>/Momentum too,
         so momentum and LARS runs resume into each other; the slot name TensorFlow's own contrib LARS optimizer
-        writes is not checked here (TensorFlow is not part of the test environment)."""
+        writes is not checked here (TensorFlow is not part of the test environment).  Adam -> <v>/Adam (m), <v>/Adam_1
+        (v) and the scalars beta1_power, beta2_power (``beta_powers()``); parity of these names with a file written
+        by TensorFlow itself is not checked here either."""
         out = []
         for p in self.params:
             name = getattr(p, "tf_name", None)
@@ -320,8 +418,15 @@ class FusedOptimizer:
             elif self.kind == "rmsprop":
                 out.append((name + "/RMSProp", st["s2"]))
                 out.append((name + "/RMSProp_1", st["s1"]))
+            elif self.kind == "adam":
+                out.append((name + "/Adam", st["s1"]))
+                out.append((name + "/Adam_1", st["s2"]))
             if "ema" in st:
                 out.append((name + "/ExponentialMovingAverage", st["ema"]))
+        if self.kind == "adam":
+            b1p, b2p = self.beta_powers()
+            out.append(("beta1_power", torch.tensor(b1p)))
+            out.append(("beta2_power", torch.tensor(b2p)))
         return out
 
     def buffer_shadows(self):

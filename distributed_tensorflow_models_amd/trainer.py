@@ -18,7 +18,7 @@ import time
 import numpy as np
 import torch
 
-from .ckpt.saver import Saver, TFVar, model_variables
+from .ckpt.saver import AdamPowerVar, Saver, TFVar, model_variables
 from .compat import logging
 from .compat.train import ExponentialDecay, LinearWarmup, PolynomialDecay, Server
 from .engine import TrainStep
@@ -108,6 +108,10 @@ LARGE_BATCH_BSP_ONLY = ("--optimizer lars and --clip_global_norm need --sync_mod
                         "update runs on owner shards from one worker's push, where no global gradient norm exists")
 
 
+ADAM_BSP_ONLY = ("--optimizer adam needs --sync_mode bsp (got %s): under asp / ssp the update runs on owner shards, "
+                 "which would need a shared count of applied updates per shard for the bias correction")
+
+
 def define_common_flags(flags, preset):
     """Flags shared by every trainer (reference flag inventory) + MI355X extras."""
     p = PRESETS[preset]
@@ -139,7 +143,11 @@ def define_common_flags(flags, preset):
             ("num_epochs_per_decay", Fl, p["decay_epochs"], "Epochs after which learning rate decays."),
             ("learning_rate_decay_factor", Fl, p["decay_factor"], "Learning rate decay factor."),
             # large-batch training (all default to the preset's behaviour)
-            ("optimizer", S, "", "sgd | momentum | rmsprop | lars (default: the preset's optimizer); lars is BSP only"),
+            ("optimizer", S, "", "sgd | momentum | rmsprop | lars | adam (default: the preset's optimizer); lars and "
+             "adam are BSP only"),
+            ("adam_beta1", Fl, 0.9, "Adam: decay of the first-moment estimate"),
+            ("adam_beta2", Fl, 0.999, "Adam: decay of the second-moment estimate"),
+            ("adam_epsilon", Fl, 1e-8, "Adam: epsilon added to sqrt(v)"),
             ("lars_eeta", Fl, 0.001, "LARS trust coefficient"),
             ("lars_epsilon", Fl, 0.0, "LARS epsilon in the trust ratio's denominator"),
             ("clip_global_norm", Fl, 0.0, "clip the gradient by this global norm (0 = off); BSP only, not with lars"),
@@ -243,13 +251,15 @@ def train(preset, flags, default_mode="bsp"):
     mode = (FLAGS.sync_mode or default_mode).lower()
     logging.set_verbosity(logging.INFO)
     optimizer = (FLAGS.optimizer or cfg["optimizer"]).lower()
-    if optimizer not in ("sgd", "momentum", "rmsprop", "lars"):
-        raise ValueError("--optimizer must be sgd, momentum, rmsprop or lars, got %r" % FLAGS.optimizer)
+    if optimizer not in ("sgd", "momentum", "rmsprop", "lars", "adam"):
+        raise ValueError("--optimizer must be sgd, momentum, rmsprop, lars or adam, got %r" % FLAGS.optimizer)
     if FLAGS.lr_decay not in ("", "exponential", "polynomial"):
         raise ValueError("--lr_decay must be exponential or polynomial, got %r" % FLAGS.lr_decay)
     if mode in ("asp", "ssp") and (optimizer == "lars" or FLAGS.clip_global_norm > 0):
         # checked before any process group or store exists: every rank fails at once
         raise ValueError(LARGE_BATCH_BSP_ONLY % mode)
+    if mode in ("asp", "ssp") and optimizer == "adam":
+        raise ValueError(ADAM_BSP_ONLY % mode)
     ps_hosts = [h for h in FLAGS.ps_hosts.split(",") if h]
     worker_hosts = [h for h in FLAGS.worker_hosts.split(",") if h]
     if FLAGS.job_name == "ps":
@@ -305,7 +315,8 @@ def train(preset, flags, default_mode="bsp"):
     if FLAGS.warmup_steps > 0:
         sched = LinearWarmup(sched, FLAGS.warmup_steps)
     opt_kw = dict(optimizer=optimizer, lr=sched(0), momentum=cfg.get("momentum", 0.9),
-                  rho=cfg.get("rmsprop_decay", 0.9), epsilon=cfg.get("rmsprop_epsilon", 1e-10))
+                  rho=cfg.get("rmsprop_decay", 0.9),
+                  epsilon=FLAGS.adam_epsilon if optimizer == "adam" else cfg.get("rmsprop_epsilon", 1e-10))
 
     # ---- engine + supervisor / checkpoints (C7, §5.4) -------------------------------------------
     from .compat.train import Supervisor, latest_checkpoint
@@ -341,19 +352,20 @@ def train(preset, flags, default_mode="bsp"):
                             timer=StepTimer() if (FLAGS.metrics_file and rank == 0 and not FLAGS.use_hipgraph)
                             else None, lars_eeta=FLAGS.lars_eeta, lars_epsilon=FLAGS.lars_epsilon,
                             clip_global_norm=FLAGS.clip_global_norm if FLAGS.clip_global_norm > 0 else None,
-                            **opt_kw)
+                            beta1=FLAGS.adam_beta1, beta2=FLAGS.adam_beta2, **opt_kw)
         vars_ = model_variables(model, step_fn.opt, gstep, **ckpt_kw)
         vars_[-1].name = cfg.get("global_step_name", "global_step")
         if path:
             Saver(vars_).restore(path)
         if world > 1:  # one collective replaces the reference's chief-init + 1 s polling of workers
-            pg.broadcast_tensors([v.tensor for v in vars_ if v.tensor.is_floating_point()] +
-                                 [b for b in model.buffers()])
+            # (Adam's beta*_power scalars are host values derived from the step count, which every rank restores)
+            pg.broadcast_tensors([v.tensor for v in vars_ if v.tensor.is_floating_point()
+                                  and not isinstance(v, AdamPowerVar)] + [b for b in model.buffers()])
         from .ops.nn import invalidate_weight_copies
         invalidate_weight_copies(model.parameters())  # bf16 compute copies follow the restored weights
         step_fn.bufsync.resync()  # the BN statistics' sync snapshot follows the restored / broadcast values
         step_fn.global_step = int(gstep)
-        step_fn.opt.num_updates = int(gstep)
+        step_fn.opt.restored(int(gstep))  # num_updates; Adam: the applied-update count from beta*_power
     elif mode in ("asp", "ssp"):
         from .engine import moving_average_buffers, prepare_compute_copies
         from .parallel.asp import ASPTrainStep, ParamStore
@@ -494,6 +506,8 @@ def train(preset, flags, default_mode="bsp"):
                         if k in ns:
                             tbw.add_scalar(k, ns[k], gs)
                 extra.update(ns)
+            if mode == "bsp" and optimizer == "adam" and metrics.f is not None:
+                extra["adam_step"] = step_fn.opt.adam_step()  # applied updates: lags global_step after a NaN skip
             if mode == "bsp" and metrics.f is not None and world > 1:
                 bms = step_fn.dp.bucket_ms()  # per-bucket all-reduce durations (RCCL timing events)
                 if bms:

@@ -8,18 +8,22 @@ event summary to ``eval_dir``.  Reference defects fixed: the checkpoint state is
 poll (C56/C57 read it once), ResNet eval runs in inference mode (C58 used is_training=True), a
 checkpoint already evaluated is not re-evaluated.
 """
+import json
 import math
 import os
 import shutil
 import time
 from datetime import datetime
 
+import numpy as np
 import torch
 
 from . import trainer
 from .ckpt.saver import Saver, TFVar, get_checkpoint_state, step_from_path
 from .models.layers import tf_variables
-from .ops import elementwise as E
+from .compat import logging
+from .ops.metrics import StreamingMetrics
+from .utils.metrics import JsonlMetrics
 from .utils.tb import SummaryWriter
 
 EVAL_DEFAULTS = {
@@ -55,6 +59,12 @@ def define_eval_flags(flags, preset):
             ("use_ema", flags.DEFINE_boolean, d[4], "restore ExponentialMovingAverage shadows"),
             ("synthetic_data", flags.DEFINE_boolean, False, "evaluate on synthetic batches"),
             ("max_evals", flags.DEFINE_integer, 0, "stop after N evaluations (0 = forever)"),
+            ("eval_loss", flags.DEFINE_boolean, False, "print and write the mean cross-entropy of the evaluation"),
+            ("eval_per_class", flags.DEFINE_boolean, False,
+             "write the mean per-class accuracy and metrics-<step>.json (all scalars and per-class arrays)"),
+            ("eval_confusion", flags.DEFINE_boolean, False,
+             "write confusion-<step>.npy and a 'Confusion matrix' image summary"),
+            ("metrics_file", flags.DEFINE_string, "", "JSONL metrics path: one line per evaluation"),
     ):
         fn(name, default, h)
         F.reset(name)
@@ -100,19 +110,73 @@ def _inputs(preset, flags, device):
 
 
 @torch.no_grad()
-def eval_once(model, data, num_examples, batch_size, top5=False):
+def _eval_once(model, data, num_examples, batch_size, metrics=None, confusion=False):
+    """``ceil(num_examples / batch_size)`` batches added to a StreamingMetrics record on the device and read ONCE
+    at the end (no host round trip per batch).  Returns (p1, r5, the fetched record)."""
     num_iter = int(math.ceil(num_examples / float(batch_size)))
-    c1 = c5 = 0
+    if metrics is not None:
+        metrics.reset()
     for _ in range(num_iter):
         x, y = data.next_batch()
         out = model(x, training=False)
         if isinstance(out, tuple):
             out = out[0]
+        if out.dtype not in (torch.float32, torch.bfloat16):
+            out = out.float()
+        if y.dtype not in (torch.int32, torch.int64):
+            y = y.long()
+        if metrics is None:
+            C = out.shape[-1]
+            metrics = StreamingMetrics(C, k=min(5, C), confusion=confusion, device=out.device)
         # tf.nn.in_top_k (ties at the boundary count as correct), HIP kernel on the GPU
-        c1 += int(E.in_top_k(out, y, 1).sum())
-        c5 += int(E.in_top_k(out, y, min(5, out.shape[-1])).sum())
+        metrics.update(out, y)
+    res = metrics.fetch()
     total = num_iter * batch_size
-    return c1 / total, c5 / total
+    return res["top1"] / total, res["topk"] / total, res
+
+
+def eval_once(model, data, num_examples, batch_size, top5=False, metrics=None):
+    """(precision @ 1, recall @ 5) over ``num_iter * batch_size`` examples.  ``metrics``: a StreamingMetrics to use
+    (reset first; its ``k`` is the k of the second value) - fetch it afterwards for the loss, the per-class counts
+    and the confusion matrix of the same pass; None: one with k = min(5, classes) is made."""
+    p1, r5, _ = _eval_once(model, data, num_examples, batch_size, metrics)
+    return p1, r5
+
+
+def _confusion_image(conf):
+    """[C, C] counts -> uint8 [C, C, 1], every row scaled to 0-255 by its own sum (an empty row stays black)."""
+    rows = conf.sum(1, keepdims=True).astype(np.float64)
+    img = np.where(rows > 0, conf / np.maximum(rows, 1.0), 0.0)
+    return np.rint(img * 255.0).astype(np.uint8)[:, :, None]
+
+
+def _write_extras(F, writer, jsonl, res, gs, p1, r5):
+    """What the --eval_* flags and --metrics_file add to one evaluation."""
+    if res["nonfinite"]:
+        logging.warning("evaluation at step %d: %d of %d examples have non-finite logits (left out of the loss and "
+                        "of the argmax counts)", gs, res["nonfinite"], res["examples"])
+    # (a ratio over nothing is NaN, which JSON cannot hold: null)
+    scalars = {n: None if res[n] != res[n] else res[n]
+               for n in ("examples", "skipped", "nonfinite", "loss_rows", "top1", "topk", "k", "argmax_correct",
+                         "loss_sum", "mean_loss", "precision_at_1", "recall_at_k", "accuracy",
+                         "mean_per_class_accuracy")}
+    if F.eval_loss:
+        print("%s: eval loss = %.4f" % (datetime.now(), res["mean_loss"]), flush=True)
+        writer.add_scalar("Loss", res["mean_loss"], gs)
+    if F.eval_per_class:
+        writer.add_scalar("Mean per-class accuracy", res["mean_per_class_accuracy"], gs)
+        doc = dict(scalars, global_step=gs)
+        for n in ("support", "top1_correct", "predicted"):
+            doc[n] = res[n].tolist()
+        doc["per_class_accuracy"] = [None if v != v else v for v in res["per_class_accuracy"].tolist()]
+        with open(os.path.join(F.eval_dir, "metrics-%d.json" % gs), "w") as f:
+            json.dump(doc, f)
+    if F.eval_confusion:
+        np.save(os.path.join(F.eval_dir, "confusion-%d.npy" % gs), res["confusion"])
+        if res["confusion"].shape[0] <= 512:  # larger matrices are saved, not drawn
+            writer.add_image("Confusion matrix", _confusion_image(res["confusion"]), gs)
+    # (eval_*: the printed values, over num_iter * batch_size; precision_at_1 / recall_at_k: over the valid rows)
+    jsonl.write(global_step=gs, eval_precision_at_1=p1, eval_recall_at_5=r5, **scalars)
 
 
 def evaluate(preset, flags):
@@ -133,6 +197,8 @@ def evaluate(preset, flags):
     os.makedirs(F.eval_dir, exist_ok=True)
     writer = SummaryWriter(F.eval_dir)
     data = _inputs(preset, flags, device)
+    extras = F.eval_loss or F.eval_per_class or F.eval_confusion or bool(F.metrics_file)
+    jsonl = JsonlMetrics(F.metrics_file or None)
     last = None
     n_evals = 0
     results = []
@@ -145,7 +211,7 @@ def evaluate(preset, flags):
             restore_for_eval(model, path, F.use_ema, prefix=cfg.get("scope_prefix", ""))
             gs = step_from_path(path)
             t0 = time.time()
-            p1, r5 = eval_once(model, data, F.num_examples, F.batch_size, top5)
+            p1, r5, res = _eval_once(model, data, F.num_examples, F.batch_size, confusion=F.eval_confusion)
             dt = time.time() - t0
             if top5:
                 print("%s: precision @ 1 = %.4f recall @ 5 = %.4f [%d examples] (%.1f examples/sec)"
@@ -154,6 +220,8 @@ def evaluate(preset, flags):
             else:
                 print("%s: precision @ 1 = %.3f, global_step: %d" % (datetime.now(), p1, gs), flush=True)
             writer.add_scalar("Precision @ 1", p1, gs)
+            if extras or res["nonfinite"]:
+                _write_extras(F, writer, jsonl, res, gs, p1, r5)
             results.append((gs, p1, r5))
             last = path
             n_evals += 1
@@ -161,4 +229,5 @@ def evaluate(preset, flags):
             break
         time.sleep(F.eval_interval_secs)
     writer.close()
+    jsonl.close()
     return results

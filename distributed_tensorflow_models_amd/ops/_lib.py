@@ -160,6 +160,11 @@ _SIGS = {
     "dtm_stats_num_buckets": (_I, []),
     "dtm_stats_limits": (None, [_P]),
     "dtm_tensor_stats": (_I, [_P, _P, _I, _I, _P, _P, _P, _P]),
+    "dtm_metrics_header_words": (_I, []),
+    "dtm_metrics_max_classes": (_I, []),
+    "dtm_metrics_max_confusion_classes": (_I, []),
+    "dtm_metrics_max_batch": (_I, []),
+    "dtm_eval_metrics": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
 }
 
 

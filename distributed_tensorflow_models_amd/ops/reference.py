@@ -175,3 +175,53 @@ def tensor_stats(x, scale=1.0):
                 max=float(fin.max()) if fin.size else float("-inf"),
                 sum=math.fsum(d.tolist()), sum_squares=math.fsum((d * d).tolist()),
                 zeros=int(np.count_nonzero(fin == 0)), nonfinite=int(v.size - fin.size))
+
+
+def eval_metrics(logits, labels, k):
+    """Plain oracle of ops.metrics.StreamingMetrics for one batch (tests only): numpy, fp64 arithmetic, one row
+    at a time, straight from the definitions (csrc/kernels/metrics.hip).  ``logits`` [B, C] (a tensor is upcast to
+    fp64 exactly), ``labels`` [B].  Returns the integer counters as Python ints, ``loss_sum`` (math.fsum of the
+    row losses), the per-class int64 arrays, ``confusion`` [C, C] and ``row_loss`` (fp64 [B], NaN where a row has
+    no loss)."""
+    import math
+
+    import numpy as np
+    if isinstance(logits, torch.Tensor):
+        logits = logits.detach().double().cpu().numpy()
+    if isinstance(labels, torch.Tensor):
+        labels = labels.detach().cpu().numpy()
+    x_all = np.asarray(logits, dtype=np.float64)
+    B, C = x_all.shape
+    out = dict(examples=0, skipped=0, nonfinite=0, loss_rows=0, top1=0, topk=0, argmax_correct=0)
+    support = np.zeros(C, np.int64)
+    top1_correct = np.zeros(C, np.int64)
+    predicted = np.zeros(C, np.int64)
+    confusion = np.zeros((C, C), np.int64)
+    row_loss = np.full(B, np.nan)
+    for r in range(B):
+        x, t = x_all[r].tolist(), int(labels[r])
+        if not 0 <= t < C:
+            out["skipped"] += 1
+            continue
+        out["examples"] += 1
+        support[t] += 1
+        greater = sum(1 for c in range(C) if x[c] > x[t])
+        if math.isfinite(x[t]) and greater < 1:
+            out["top1"] += 1
+            top1_correct[t] += 1
+        if math.isfinite(x[t]) and greater < k:
+            out["topk"] += 1
+        if not all(math.isfinite(v) for v in x):
+            out["nonfinite"] += 1
+            continue
+        m = max(x)
+        pred = min(c for c in range(C) if x[c] == m)
+        predicted[pred] += 1
+        confusion[t, pred] += 1
+        out["argmax_correct"] += int(pred == t)
+        out["loss_rows"] += 1
+        row_loss[r] = math.log(math.fsum(math.exp(v - m) for v in x)) + m - x[t]
+    out["loss_sum"] = math.fsum(v for v in row_loss if not math.isnan(v))
+    out.update(support=support, top1_correct=top1_correct, predicted=predicted, confusion=confusion,
+               row_loss=row_loss)
+    return out

@@ -24,13 +24,24 @@ registered and checkpointed like every other variable):
 
 Deviation (documented): TF's optional ``freeze_bn_delay`` (switch to moving moments with the
 correction factors after N steps) is not implemented -- the reference's scripts never set it.
-Quantisation runs in fp32 torch ops (the model is small; not a hot path).
+By default quantisation runs in fp32 torch ops.  ``QuantConfig(fused=True)`` routes both quantisers through the
+device passes of ``ops/fakequant.py`` (csrc/kernels/fakequant.hip): three launches per quantiser, the delay decided on
+the device from a device step counter, so the step can be captured into a hipGraph and replayed across ``quant_delay``.
+Same variables, names and arithmetic (checkpoints interchange); differences of the fused path:
+
+* a batch with a NaN or +-Inf element leaves the range variables untouched and is counted (``nonfinite_batches``)
+  instead of poisoning them for the rest of the run;
+* the weight quantiser tracks its last-value range before the delay too (the unfused one starts at the delay), and
+  with ``is_training=False`` it reads the recorded range as TF's eval graph does (the unfused one recomputes it from
+  the weights).
 """
 import torch
 
 
 class QuantConfig:
-    def __init__(self, quant_delay=0, num_bits=8, ema_decay=0.999, is_training=True, fold_bn=True):
+    def __init__(self, quant_delay=0, num_bits=8, ema_decay=0.999, is_training=True, fold_bn=True, fused=False):
+        self.fused = bool(fused)  # quantisers as device passes with device-side state (ops/fakequant.py)
+        self._counter = None      # fused: int64 device count of training forwards (what ``step`` counts on the host)
         self.fold_bn = bool(fold_bn)  # fold slim.batch_norm into the producing conv's weights (TF default)
         self.quant_delay = int(quant_delay or 0)
         self.num_bits = int(num_bits)
@@ -43,6 +54,29 @@ class QuantConfig:
 
     def advance(self, n=1):
         self.step += n
+
+    def counter(self, device):
+        """Fused path: the device step counter, created from the steps seen so far on first use (never inside a
+        hipGraph capture: the warm-up steps of ``TrainStep`` run eagerly)."""
+        device = torch.device(device)
+        c = self._counter
+        if c is None or c.device != device:
+            if device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("QuantConfig.counter(): first call on this device inside a hipGraph capture")
+            self._counter = c = torch.tensor([self.steps_done()], dtype=torch.int64, device=device)
+        return c
+
+    def advance_fused(self):
+        """One training forward on the fused path: counter += 1 in stream order (captured and replayed with the
+        step); the host's ``step`` is advanced by ``advance`` as on the unfused path."""
+        if self._counter is not None:
+            from ..ops import fakequant
+            fakequant.advance(self._counter)
+
+    def steps_done(self):
+        """Training forwards seen: the device counter where one exists (a device read: logged steps and tests
+        only), else the host's ``step``."""
+        return int(self._counter) if self._counter is not None else self.step
 
 
 def create_training_graph(model, quant_delay=0, num_bits=8):
@@ -89,6 +123,9 @@ def quantize_weights(w, var_fn, cfg):
     """w: fp32 master (Parameter); var_fn(name, init) creates/reuses the layer scope's state."""
     vmin = var_fn("weights_quant/min", 0.0)
     vmax = var_fn("weights_quant/max", 0.0)
+    if cfg.fused:
+        from ..ops import fakequant as FQ
+        return FQ.quantize(w, vmin, vmax, cfg, FQ.WEIGHTS if cfg.is_training else FQ.FROZEN, narrow=True)
     if not cfg.active():
         return w
     with torch.no_grad():
@@ -101,6 +138,10 @@ def quantize_weights(w, var_fn, cfg):
 def quantize_activations(y, var_fn, cfg, training):
     vmin = var_fn("act_quant/min", 0.0)
     vmax = var_fn("act_quant/max", 6.0)
+    if cfg.fused:
+        from ..ops import fakequant as FQ
+        return FQ.quantize(y, vmin, vmax, cfg, FQ.ACT_TRAIN if (training and cfg.is_training) else FQ.FROZEN,
+                           narrow=False)
     if training and cfg.is_training:
         with torch.no_grad():
             d = cfg.ema_decay

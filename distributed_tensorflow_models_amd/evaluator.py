@@ -189,7 +189,7 @@ def evaluate(preset, flags):
         kw["depth_multiplier"] = F.depth_multiplier
     if "quantize" in F and F.quantize:  # create_eval_graph (mobilenet_v1_eval.py:126-127)
         from .compat.quantize import QuantConfig
-        kw["quantize"] = QuantConfig(is_training=False)
+        kw["quantize"] = QuantConfig(is_training=False, fused=bool("quant_fused" in F and F.quant_fused))
     model = trainer.build_model_for_eval(preset, **kw).to(device)
     model.eval()
     if os.path.isdir(F.eval_dir):

@@ -62,5 +62,7 @@ class SlimModel(torch.nn.Module):
         out = self._run(x, training, end_points)
         q = self.store.quant
         if training and q is not None and q.is_training:
+            if q.fused:
+                q.advance_fused()  # the same event on the device counter the fused quantisers read
             q.advance()  # one training forward = one step of the quant_delay count
         return out

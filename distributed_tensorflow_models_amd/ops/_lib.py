@@ -165,6 +165,15 @@ _SIGS = {
     "dtm_metrics_max_confusion_classes": (_I, []),
     "dtm_metrics_max_batch": (_I, []),
     "dtm_eval_metrics": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "dtm_fq_rec_words": (_I, []),
+    "dtm_fq_partial_stride": (_I, []),
+    "dtm_fq_threads": (_I, []),
+    "dtm_fq_grid": (_I, [_L, _I]),
+    "dtm_fq_range": (_I, [_P, _I, _L, _P, _P]),
+    "dtm_fq_finalize": (_I, [_P, _I, _P, _P, _P, _P, _I, _F, _F, _I, _I, _L, _I, _P]),
+    "dtm_fq_apply": (_I, [_P, _P, _I, _L, _P, _P]),
+    "dtm_fq_apply_bwd": (_I, [_P, _P, _P, _I, _L, _P, _P]),
+    "dtm_fq_advance": (_I, [_P, _P]),
 }
 
 

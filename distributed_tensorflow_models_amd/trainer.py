@@ -291,7 +291,12 @@ def train(preset, flags, default_mode="bsp"):
         # tf.contrib.quantize.create_training_graph(quant_delay=get_quant_delay())
         # (reference vgg/nets/mobilenet_v1_train.py:66-73,138-139): quantise at once when fine-tuning
         from .compat.quantize import QuantConfig
-        mkw["quantize"] = QuantConfig(quant_delay=0 if FLAGS.fine_tune_checkpoint else FLAGS.quant_delay)
+        quant_fused = bool("quant_fused" in FLAGS and FLAGS.quant_fused)
+        mkw["quantize"] = QuantConfig(quant_delay=0 if FLAGS.fine_tune_checkpoint else FLAGS.quant_delay,
+                                      fused=quant_fused)
+        if FLAGS.use_hipgraph and not quant_fused:
+            logging.warning("--quantize --use_hipgraph without --quant_fused: the captured step freezes the side of "
+                            "--quant_delay it was captured on (quantisation never starts, or never stops)")
     model = nets_factory.build(cfg["model"], num_classes=cfg["num_classes"], **mkw).to(device)
     if cfg.get("wd_all") is not None:  # loss += wd * sum(l2_loss(v) for v in trainable_variables())
         for p in model.parameters():
@@ -508,6 +513,11 @@ def train(preset, flags, default_mode="bsp"):
                 extra.update(ns)
             if mode == "bsp" and optimizer == "adam" and metrics.f is not None:
                 extra["adam_step"] = step_fn.opt.adam_step()  # applied updates: lags global_step after a NaN skip
+            if metrics.f is not None and getattr(mkw.get("quantize"), "fused", False):
+                # device reads, after the logged step's synchronisation above
+                from .ops import fakequant
+                extra["quant_step"] = mkw["quantize"].steps_done()
+                extra["quant_nonfinite_batches"] = fakequant.nonfinite_batches(model)
             if mode == "bsp" and metrics.f is not None and world > 1:
                 bms = step_fn.dp.bucket_ms()  # per-bucket all-reduce durations (RCCL timing events)
                 if bms:

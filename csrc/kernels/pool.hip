@@ -4,7 +4,16 @@
 //  * avg pool: TF SAME semantics divide by the number of in-bounds taps (count_pad=0), or
 //    by kh*kw (count_pad=1).
 //  * global mean over H*W (slim resnet 'pool5', reference vgg/nets/resnet_v1.py:244).
-// Eight channels per lane (16-B loads) when C % 8 == 0.
+// Layout of this file:
+//  1. helpers: 8-channel unpack / argmax-byte pack, the index policies (Idx32: magic-number division, Idx64: plain
+//     64-bit division) and the flat index -> (pixel, channel chunk, n, row, col) split every kernel shares;
+//  2. the generic bodies, each written once over <channels per lane V, index policy>: max pool fwd (optionally with
+//     BN-apply + ReLU on the tap) / bwd, avg pool fwd / bwd, global mean bwd.  Built as (V = 8, Idx32) when
+//     C % 8 == 0 and the tensors stay below 2^31 elements, (V = 8, Idx64) above that, (V = 1, Idx64) otherwise;
+//  3. the shape specialisations, each a different algorithm that earned its place with a measurement: the 5x5/3
+//     VALID avg pool, the 8-channel global mean fwd, the BN+ReLU max-pool gather bwd, 3x3/2 max pools, 3x3/1 avg
+//     pools.  They hold their results bit-identical to the generic bodies (tests/test_kernels_gpu.py);
+//  4. host dispatch: fits32 / k3s2_ok / k3s1_ok pick the kernel, one launch wrapper per generic body.
 #include "common.h"
 
 namespace dtm {
@@ -15,15 +24,34 @@ struct PoolArgs {
 // first window index p >= 0 with p*S >= num  (num = h + pad - k + 1)
 __device__ __forceinline__ int first_win(int num, int S) { return num <= 0 ? 0 : (num + S - 1) / S; }
 
+// eight bf16 of a 16-B chunk as floats, in memory order
+__device__ __forceinline__ void unpack8(uint4 u, float* f) {
+  f[0] = lo_bf(u.x); f[1] = hi_bf(u.x); f[2] = lo_bf(u.y); f[3] = hi_bf(u.y);
+  f[4] = lo_bf(u.z); f[5] = hi_bf(u.z); f[6] = lo_bf(u.w); f[7] = hi_bf(u.w);
+}
+__device__ __forceinline__ void add8(float* acc, uint4 u) {
+  float f[8];
+  unpack8(u, f);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) acc[e] += f[e];
+}
+// BN scale and shift of channels cv .. cv + 7 (ss = [scale; shift; ...], rows of C floats)
+__device__ __forceinline__ void load_ss8(const float* __restrict__ ss, int C, uint32_t cv, float* sc, float* sh) {
+  const float4 s0 = *(const float4*)(ss + cv), s1 = *(const float4*)(ss + cv + 4);
+  const float4 h0 = *(const float4*)(ss + C + cv), h1 = *(const float4*)(ss + C + cv + 4);
+  sc[0] = s0.x; sc[1] = s0.y; sc[2] = s0.z; sc[3] = s0.w; sc[4] = s1.x; sc[5] = s1.y; sc[6] = s1.z; sc[7] = s1.w;
+  sh[0] = h0.x; sh[1] = h0.y; sh[2] = h0.z; sh[3] = h0.w; sh[4] = h1.x; sh[5] = h1.y; sh[6] = h1.z; sh[7] = h1.w;
+}
+// the argmax bytes of 8 channels as one 8-B store, and byte e of such a load
+__device__ __forceinline__ uint2 pack_arg8(const uint32_t* bi) {
+  return make_uint2(bi[0] | bi[1] << 8 | bi[2] << 16 | bi[3] << 24, bi[4] | bi[5] << 8 | bi[6] << 16 | bi[7] << 24);
+}
+__device__ __forceinline__ uint32_t arg_byte(uint2 v, int e) { return ((e < 4 ? v.x : v.y) >> (8 * (e & 3))) & 0xffu; }
+
 template <int V>
 __device__ __forceinline__ void ld(const bf16_t* p, float* f) {
-  if constexpr (V == 8) {
-    uint4 u = *(const uint4*)p;
-    f[0] = lo_bf(u.x); f[1] = hi_bf(u.x); f[2] = lo_bf(u.y); f[3] = hi_bf(u.y);
-    f[4] = lo_bf(u.z); f[5] = hi_bf(u.z); f[6] = lo_bf(u.w); f[7] = hi_bf(u.w);
-  } else {
-    f[0] = bf2f(*p);
-  }
+  if constexpr (V == 8) unpack8(*(const uint4*)p, f);
+  else f[0] = bf2f(*p);
 }
 template <int V>
 __device__ __forceinline__ void st(bf16_t* p, const float* f) {
@@ -34,52 +62,91 @@ __device__ __forceinline__ void st(bf16_t* p, const float* f) {
   }
 }
 
-template <int V>
-__global__ __launch_bounds__(256) void maxpool_fwd_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ y,
-                                                          uint8_t* __restrict__ arg, PoolArgs a) {
-  const int cols = a.C / V;
-  const long total = (long)a.N * a.P * a.Q * cols;
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    int cv = (int)(i % cols) * V;
-    long o = i / cols;
-    int q = o % a.Q; long t = o / a.Q;
-    int p = t % a.P; int n = (int)(t / a.P);
-    float best[V];
-    uint8_t bi[V];
+// ---- index policies: how a kernel divides its flat index.  Idx32: 32-bit magic-number division (every index below
+// 2^31; the 64-bit divisions dominated the generic kernels' time: 30 us for the backward of Inception's 5x5/3
+// aux-head pool over 17x17x768).  Idx64: plain 64-bit division, for tensors past that and for one-channel lanes. ----
+struct Idx32 {
+  typedef uint32_t T;
+  FastDiv f;
+  __device__ __forceinline__ T div(T n) const { return fdiv(n, f); }
+  __device__ __forceinline__ T d() const { return f.d; }
+  static Idx32 make(int d) { return Idx32{make_fastdiv((uint32_t)d)}; }
+};
+struct Idx64 {
+  typedef long T;
+  long dv;
+  __device__ __forceinline__ T div(T n) const { return n / dv; }
+  __device__ __forceinline__ T d() const { return dv; }
+  static Idx64 make(int d) { return Idx64{(long)d}; }
+};
+// flat index i over [n][row][col][C / V] -> pixel o = (n * rows + row) * cols + col and channel offset cv
+template <class Index>
+struct Split {
+  typename Index::T o, n;
+  int cv, row, col;
+};
+template <int V, class Index>
+__device__ __forceinline__ Split<Index> split(typename Index::T i, const Index& fchunks, const Index& fcols,
+                                              const Index& frows) {
+  Split<Index> s;
+  s.o = fchunks.div(i);
+  s.cv = (int)(i - s.o * fchunks.d()) * V;
+  const typename Index::T t = fcols.div(s.o);
+  s.col = (int)(s.o - t * fcols.d());
+  s.n = frows.div(t);
+  s.row = (int)(t - s.n * frows.d());
+  return s;
+}
+
+// ---- generic bodies (any window, stride and padding), grid-stride over `total` lanes ----
+// BN: y = maxpool(relu(x*scale + shift)), the normalised activation formed on the fly from the raw conv output and
+// never stored (ResNet stem: conv1 -> BN -> ReLU -> pool).  Strict > scan in (r, s) order: first-maximum argmax.
+template <int V, bool BN, class Index>
+__global__ __launch_bounds__(256) void maxpool_fwd_kernel(const bf16_t* __restrict__ x, const float* __restrict__ ss,
+                                                          bf16_t* __restrict__ y, uint8_t* __restrict__ arg, PoolArgs a,
+                                                          Index fchunks, Index fQ, Index fP, typename Index::T total) {
+  static_assert(!BN || V == 8, "the BN+ReLU tap is built for 8-channel lanes only");
+  typedef typename Index::T T;
+  for (T i = blockIdx.x * (T)256 + threadIdx.x; i < total; i += gridDim.x * (T)256) {
+    const Split<Index> k = split<V>(i, fchunks, fQ, fP);
+    float sc[8], sh[8], best[V];
+    uint32_t bi[V];
+    if constexpr (BN) load_ss8(ss, a.C, k.cv, sc, sh);
 #pragma unroll
     for (int e = 0; e < V; ++e) { best[e] = -INFINITY; bi[e] = 0; }
     for (int r = 0; r < a.KH; ++r) {
-      int h = p * a.SH - a.PH + r;
+      const int h = k.row * a.SH - a.PH + r;
       if (h < 0 || h >= a.H) continue;
       for (int s = 0; s < a.KW; ++s) {
-        int w = q * a.SW - a.PW + s;
+        const int w = k.col * a.SW - a.PW + s;
         if (w < 0 || w >= a.W) continue;
         float f[V];
-        ld<V>(x + (((long)n * a.H + h) * a.W + w) * a.C + cv, f);
+        ld<V>(x + (((size_t)k.n * a.H + h) * a.W + w) * a.C + k.cv, f);
 #pragma unroll
-        for (int e = 0; e < V; ++e)
-          if (f[e] > best[e]) { best[e] = f[e]; bi[e] = (uint8_t)(r * a.KW + s); }
+        for (int e = 0; e < V; ++e) {
+          float v = f[e];
+          if constexpr (BN) v = fmaxf(fmaf(f[e], sc[e], sh[e]), 0.f);
+          if (v > best[e]) { best[e] = v; bi[e] = (uint32_t)(r * a.KW + s); }
+        }
       }
     }
-    st<V>(y + o * a.C + cv, best);
-    if (arg) {
-#pragma unroll
-      for (int e = 0; e < V; ++e) arg[o * a.C + cv + e] = bi[e];
+    st<V>(y + (size_t)k.o * a.C + k.cv, best);
+    if (BN || arg) {
+      if constexpr (V == 8) *(uint2*)(arg + (size_t)k.o * a.C + k.cv) = pack_arg8(bi);
+      else arg[(size_t)k.o * a.C + k.cv] = (uint8_t)bi[0];
     }
   }
 }
 
 // dx[n,h,w,c] = sum over windows (p,q) covering (h,w) whose argmax is (h,w) of dy[n,p,q,c]
-template <int V>
+template <int V, class Index>
 __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const bf16_t* __restrict__ dy, const uint8_t* __restrict__ arg,
-                                                          bf16_t* __restrict__ dx, PoolArgs a) {
-  const int cols = a.C / V;
-  const long total = (long)a.N * a.H * a.W * cols;
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    int cv = (int)(i % cols) * V;
-    long o = i / cols;
-    int w = o % a.W; long t = o / a.W;
-    int h = t % a.H; int n = (int)(t / a.H);
+                                                          bf16_t* __restrict__ dx, PoolArgs a, Index fchunks, Index fW,
+                                                          Index fH, typename Index::T total) {
+  typedef typename Index::T T;
+  for (T i = blockIdx.x * (T)256 + threadIdx.x; i < total; i += gridDim.x * (T)256) {
+    const Split<Index> k = split<V>(i, fchunks, fW, fH);
+    const int h = k.row, w = k.col;
     float acc[V];
 #pragma unroll
     for (int e = 0; e < V; ++e) acc[e] = 0.f;
@@ -92,7 +159,7 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const bf16_t* __restri
       for (int q = qlo; q <= min(qhi, a.Q - 1); ++q) {
         int s = w - (q * a.SW - a.PW);
         if (s < 0 || s >= a.KW) continue;
-        long oo = (((long)n * a.P + p) * a.Q + q) * a.C + cv;
+        long oo = (((long)k.n * a.P + p) * a.Q + q) * a.C + k.cv;
         float g[V];
         ld<V>(dy + oo, g);
         uint8_t want = (uint8_t)(r * a.KW + s);
@@ -101,127 +168,55 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const bf16_t* __restri
           if (arg[oo + e] == want) acc[e] += g[e];
       }
     }
-    st<V>(dx + o * a.C + cv, acc);
+    st<V>(dx + (long)k.o * a.C + k.cv, acc);
   }
 }
 
-template <int V>
+// (addresses in the index policy's width: 32-bit under Idx32)
+template <int V, class Index>
 __global__ __launch_bounds__(256) void avgpool_fwd_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, PoolArgs a,
-                                                          int count_pad) {
-  const int cols = a.C / V;
-  const long total = (long)a.N * a.P * a.Q * cols;
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    int cv = (int)(i % cols) * V;
-    long o = i / cols;
-    int q = o % a.Q; long t = o / a.Q;
-    int p = t % a.P; int n = (int)(t / a.P);
+                                                          int count_pad, Index fchunks, Index fQ, Index fP,
+                                                          typename Index::T total) {
+  typedef typename Index::T T;
+  for (T i = blockIdx.x * (T)256 + threadIdx.x; i < total; i += gridDim.x * (T)256) {
+    const Split<Index> k = split<V>(i, fchunks, fQ, fP);
     float acc[V];
 #pragma unroll
     for (int e = 0; e < V; ++e) acc[e] = 0.f;
     int cnt = 0;
     for (int r = 0; r < a.KH; ++r) {
-      int h = p * a.SH - a.PH + r;
+      const int h = k.row * a.SH - a.PH + r;
       if (h < 0 || h >= a.H) continue;
       for (int s = 0; s < a.KW; ++s) {
-        int w = q * a.SW - a.PW + s;
+        const int w = k.col * a.SW - a.PW + s;
         if (w < 0 || w >= a.W) continue;
         float f[V];
-        ld<V>(x + (((long)n * a.H + h) * a.W + w) * a.C + cv, f);
+        ld<V>(x + ((k.n * a.H + h) * a.W + w) * a.C + k.cv, f);
 #pragma unroll
         for (int e = 0; e < V; ++e) acc[e] += f[e];
         ++cnt;
       }
     }
-    float inv = 1.f / (float)(count_pad ? a.KH * a.KW : max(cnt, 1));
+    const float inv = 1.f / (float)(count_pad ? a.KH * a.KW : max(cnt, 1));
 #pragma unroll
     for (int e = 0; e < V; ++e) acc[e] *= inv;
-    st<V>(y + o * a.C + cv, acc);
+    st<V>(y + k.o * a.C + k.cv, acc);
   }
 }
 
-template <int V>
+// The backward can add into dx (accum != 0): the aux head's pool gradient folded into the block-input gradient the
+// main path produced (ops/nn.py avg_pool grad_tail) instead of a separate add over the whole map.
+template <int V, class Index>
 __global__ __launch_bounds__(256) void avgpool_bwd_kernel(const bf16_t* __restrict__ dy, bf16_t* __restrict__ dx, PoolArgs a,
-                                                          int count_pad) {
-  const int cols = a.C / V;
-  const long total = (long)a.N * a.H * a.W * cols;
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    int cv = (int)(i % cols) * V;
-    long o = i / cols;
-    int w = o % a.W; long t = o / a.W;
-    int h = t % a.H; int n = (int)(t / a.H);
+                                                          int count_pad, int accum, Index fchunks, Index fW, Index fH,
+                                                          typename Index::T total) {
+  typedef typename Index::T T;
+  for (T i = blockIdx.x * (T)256 + threadIdx.x; i < total; i += gridDim.x * (T)256) {
+    const Split<Index> k = split<V>(i, fchunks, fW, fH);
+    const int h = k.row, w = k.col;
     float acc[V];
 #pragma unroll
     for (int e = 0; e < V; ++e) acc[e] = 0.f;
-    int plo = first_win(h + a.PH - a.KH + 1, a.SH), phi = min(a.P - 1, (h + a.PH) / a.SH);
-    int qlo = first_win(w + a.PW - a.KW + 1, a.SW), qhi = min(a.Q - 1, (w + a.PW) / a.SW);
-    for (int p = plo; p <= phi; ++p) {
-      int h0 = p * a.SH - a.PH;
-      if (h < h0 || h >= h0 + a.KH) continue;
-      int hc = min(h0 + a.KH, a.H) - max(h0, 0);
-      for (int q = qlo; q <= qhi; ++q) {
-        int w0 = q * a.SW - a.PW;
-        if (w < w0 || w >= w0 + a.KW) continue;
-        int wcnt = min(w0 + a.KW, a.W) - max(w0, 0);
-        float inv = 1.f / (float)(count_pad ? a.KH * a.KW : max(hc * wcnt, 1));
-        float g[V];
-        ld<V>(dy + (((long)n * a.P + p) * a.Q + q) * a.C + cv, g);
-#pragma unroll
-        for (int e = 0; e < V; ++e) acc[e] += g[e] * inv;
-      }
-    }
-    st<V>(dx + o * a.C + cv, acc);
-  }
-}
-
-// The generic avg pool with 8 channels per lane and 32-bit magic-number index math (the 64-bit divisions of the
-// V-template forms above dominated their time: 30 us for the backward of Inception's 5x5/3 aux-head pool over
-// 17x17x768).  Same tap order and divisor as those, so the results match them exactly.  The backward can add into
-// dx (accum != 0): the aux head's pool gradient folded into the block-input gradient the main path produced
-// (ops/nn.py avg_pool grad_tail) instead of a separate add over the whole map.
-__global__ __launch_bounds__(256) void avgpool_fwd8_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ y,
-                                                           PoolArgs a, int count_pad, FastDiv fcols, FastDiv fQ,
-                                                           FastDiv fP, int total) {
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
-    const uint32_t o = fdiv(i, fcols);
-    const int cv = (int)(i - o * fcols.d) * 8;
-    const uint32_t t = fdiv(o, fQ);
-    const int q = (int)(o - t * fQ.d);
-    const int n = (int)fdiv(t, fP), p = (int)(t - n * fP.d);
-    float acc[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) acc[e] = 0.f;
-    int cnt = 0;
-    for (int r = 0; r < a.KH; ++r) {
-      const int h = p * a.SH - a.PH + r;
-      if (h < 0 || h >= a.H) continue;
-      for (int s = 0; s < a.KW; ++s) {
-        const int w = q * a.SW - a.PW + s;
-        if (w < 0 || w >= a.W) continue;
-        float f[8];
-        ld<8>(x + ((n * a.H + h) * a.W + w) * a.C + cv, f);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) acc[e] += f[e];
-        ++cnt;
-      }
-    }
-    const float inv = 1.f / (float)(count_pad ? a.KH * a.KW : max(cnt, 1));
-#pragma unroll
-    for (int e = 0; e < 8; ++e) acc[e] *= inv;
-    st<8>(y + o * a.C + cv, acc);
-  }
-}
-__global__ __launch_bounds__(256) void avgpool_bwd8_kernel(const bf16_t* __restrict__ dy, bf16_t* __restrict__ dx,
-                                                           PoolArgs a, int count_pad, int accum, FastDiv fcols,
-                                                           FastDiv fW, FastDiv fH, int total) {
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
-    const uint32_t o = fdiv(i, fcols);
-    const int cv = (int)(i - o * fcols.d) * 8;
-    const uint32_t t = fdiv(o, fW);
-    const int w = (int)(o - t * fW.d);
-    const int n = (int)fdiv(t, fH), h = (int)(t - n * fH.d);
-    float acc[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) acc[e] = 0.f;
     const int plo = first_win(h + a.PH - a.KH + 1, a.SH), phi = min(a.P - 1, (h + a.PH) / a.SH);
     const int qlo = first_win(w + a.PW - a.KW + 1, a.SW), qhi = min(a.Q - 1, (w + a.PW) / a.SW);
     for (int p = plo; p <= phi; ++p) {
@@ -233,22 +228,51 @@ __global__ __launch_bounds__(256) void avgpool_bwd8_kernel(const bf16_t* __restr
         if (w < w0 || w >= w0 + a.KW) continue;
         const int wcnt = min(w0 + a.KW, a.W) - max(w0, 0);
         const float inv = 1.f / (float)(count_pad ? a.KH * a.KW : max(hc * wcnt, 1));
-        float g[8];
-        ld<8>(dy + ((n * a.P + p) * a.Q + q) * a.C + cv, g);
+        float g[V];
+        ld<V>(dy + ((k.n * a.P + p) * a.Q + q) * a.C + k.cv, g);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) acc[e] += g[e] * inv;
+        for (int e = 0; e < V; ++e) acc[e] += g[e] * inv;
       }
     }
     if (accum) {
-      float f[8];
-      ld<8>(dx + o * a.C + cv, f);
+      float f[V];
+      ld<V>(dx + k.o * a.C + k.cv, f);
 #pragma unroll
-      for (int e = 0; e < 8; ++e) acc[e] += f[e];
+      for (int e = 0; e < V; ++e) acc[e] += f[e];
     }
-    st<8>(dx + o * a.C + cv, acc);
+    st<V>(dx + k.o * a.C + k.cv, acc);
   }
 }
 
+// global mean backward: dx[n][hw][c] = dy[n][c] / HW.  One lane per V-channel output chunk, no grid-stride loop
+// (a grid-stride form with 64-bit divisions spent its time in them: 27 us Inception / 40 us ResNet-50 for a write
+// of 17 / 51 MB).
+template <typename TI, int V, class Index>
+__global__ __launch_bounds__(256) void global_avg_bwd_kernel(const TI* __restrict__ dy, bf16_t* __restrict__ dx, int C,
+                                                             Index fchunks, Index fHW, typename Index::T total,
+                                                             float inv) {
+  typedef typename Index::T T;
+  const T i = blockIdx.x * (T)256 + threadIdx.x;
+  if (i >= total) return;
+  const T o = fchunks.div(i);  // pixel n*HW + hw
+  const int cv = (int)(i - o * fchunks.d()) * V;
+  const int n = (int)fHW.div(o);
+  float g[V];
+  if constexpr (sizeof(TI) == 2) {
+    ld<V>((const bf16_t*)dy + (long)n * C + cv, g);
+  } else if constexpr (V == 8) {
+    const float4* q = (const float4*)((const float*)dy + (long)n * C + cv);
+    const float4 a = q[0], b = q[1];
+    g[0] = a.x; g[1] = a.y; g[2] = a.z; g[3] = a.w; g[4] = b.x; g[5] = b.y; g[6] = b.z; g[7] = b.w;
+  } else {
+    g[0] = dy[(long)n * C + cv];
+  }
+#pragma unroll
+  for (int e = 0; e < V; ++e) g[e] *= inv;
+  st<V>(dx + (long)o * C + cv, g);
+}
+
+// ---- specialisations ----
 // VALID K x K / stride S average pool with every window in bounds (Inception's 5x5/3 aux-head pool): the tap
 // loops are compile-time, so a lane issues all its loads back to back instead of one dependent load per runtime
 // loop trip (the generic kernels above were load-latency bound: 18 us forward / 29 us backward for that pool).
@@ -256,15 +280,11 @@ __global__ __launch_bounds__(256) void avgpool_bwd8_kernel(const bf16_t* __restr
 // divisor as the generic kernels, so the results match them bit for bit.
 template <int K>
 __global__ __launch_bounds__(256) void avgpool_fwd_valid_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ y,
-                                                                PoolArgs a, FastDiv fcols, FastDiv fQ, FastDiv fP,
-                                                                int total) {
+                                                                PoolArgs a, Idx32 fcols, Idx32 fQ, Idx32 fP, int total) {
   const int i = xcd_remap(blockIdx.x, gridDim.x) * 256 + threadIdx.x;  // (overlapping windows: one L2)
   if (i >= total) return;
-  const uint32_t o = fdiv(i, fcols);
-  const int cv = (int)(i - o * fcols.d) * 8;
-  const uint32_t t = fdiv(o, fQ);
-  const int q = (int)(o - t * fQ.d);
-  const int n = (int)fdiv(t, fP), p = (int)(t - n * fP.d);
+  const Split<Idx32> k = split<8>((uint32_t)i, fcols, fQ, fP);
+  const int n = (int)k.n, p = k.row, q = k.col, cv = k.cv;
   const bf16_t* base = x + ((n * a.H + p * a.SH) * a.W + q * a.SW) * a.C + cv;
   uint4 v[K * K];
 #pragma unroll
@@ -275,28 +295,21 @@ __global__ __launch_bounds__(256) void avgpool_fwd_valid_kernel(const bf16_t* __
 #pragma unroll
   for (int e = 0; e < 8; ++e) acc[e] = 0.f;
 #pragma unroll
-  for (int k = 0; k < K * K; ++k) {
-    const uint4 u = v[k];
-    acc[0] += lo_bf(u.x); acc[1] += hi_bf(u.x); acc[2] += lo_bf(u.y); acc[3] += hi_bf(u.y);
-    acc[4] += lo_bf(u.z); acc[5] += hi_bf(u.z); acc[6] += lo_bf(u.w); acc[7] += hi_bf(u.w);
-  }
+  for (int t = 0; t < K * K; ++t) add8(acc, v[t]);
   const float inv = 1.f / (float)(K * K);
 #pragma unroll
   for (int e = 0; e < 8; ++e) acc[e] *= inv;
-  st<8>(y + o * a.C + cv, acc);
+  st<8>(y + k.o * a.C + cv, acc);
 }
 template <int K, int S>
 __global__ __launch_bounds__(256) void avgpool_bwd_valid_kernel(const bf16_t* __restrict__ dy, bf16_t* __restrict__ dx,
-                                                                PoolArgs a, int accum, FastDiv fcols, FastDiv fW,
-                                                                FastDiv fH, int total, const bf16_t* __restrict__ zero) {
+                                                                PoolArgs a, int accum, Idx32 fcols, Idx32 fW, Idx32 fH,
+                                                                int total, const bf16_t* __restrict__ zero) {
   constexpr int MW = (K + S - 1) / S;  // windows covering a pixel, per dimension, at most
   const int i = xcd_remap(blockIdx.x, gridDim.x) * 256 + threadIdx.x;  // (a dy chunk's 25 readers: one L2)
   if (i >= total) return;
-  const uint32_t o = fdiv(i, fcols);
-  const int cv = (int)(i - o * fcols.d) * 8;
-  const uint32_t t = fdiv(o, fW);
-  const int w = (int)(o - t * fW.d);
-  const int n = (int)fdiv(t, fH), h = (int)(t - n * fH.d);
+  const Split<Idx32> k = split<8>((uint32_t)i, fcols, fW, fH);
+  const int n = (int)k.n, h = k.row, w = k.col, cv = k.cv;
   const int plo = first_win(h - K + 1, S), phi = min(a.P - 1, h / S);
   const int qlo = first_win(w - K + 1, S), qhi = min(a.Q - 1, w / S);
   uint4 g[MW * MW];
@@ -309,7 +322,7 @@ __global__ __launch_bounds__(256) void avgpool_bwd_valid_kernel(const bf16_t* __
       g[dp * MW + dq] = *(const uint4*)src;
     }
   uint4 prev = make_uint4(0, 0, 0, 0);
-  if (accum) prev = *(const uint4*)(dx + o * a.C + cv);
+  if (accum) prev = *(const uint4*)(dx + k.o * a.C + cv);
   float acc[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) acc[e] = 0.f;
@@ -319,15 +332,13 @@ __global__ __launch_bounds__(256) void avgpool_bwd_valid_kernel(const bf16_t* __
 #pragma unroll
     for (int dq = 0; dq < MW; ++dq) {
       if (plo + dp > phi || qlo + dq > qhi) continue;
-      const uint4 u = g[dp * MW + dq];
-      acc[0] += lo_bf(u.x) * inv; acc[1] += hi_bf(u.x) * inv; acc[2] += lo_bf(u.y) * inv; acc[3] += hi_bf(u.y) * inv;
-      acc[4] += lo_bf(u.z) * inv; acc[5] += hi_bf(u.z) * inv; acc[6] += lo_bf(u.w) * inv; acc[7] += hi_bf(u.w) * inv;
+      float f[8];
+      unpack8(g[dp * MW + dq], f);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) acc[e] += f[e] * inv;
     }
-  if (accum) {
-    acc[0] += lo_bf(prev.x); acc[1] += hi_bf(prev.x); acc[2] += lo_bf(prev.y); acc[3] += hi_bf(prev.y);
-    acc[4] += lo_bf(prev.z); acc[5] += hi_bf(prev.z); acc[6] += lo_bf(prev.w); acc[7] += hi_bf(prev.w);
-  }
-  st<8>(dx + o * a.C + cv, acc);
+  if (accum) add8(acc, prev);
+  st<8>(dx + k.o * a.C + cv, acc);
 }
 
 // global mean over H*W: x[N][HW][C] -> y[N][C] (fp32 out, or bf16 when it only feeds the logits GEMM: the cast
@@ -344,26 +355,10 @@ __global__ __launch_bounds__(256) void global_avg_fwd_kernel(const bf16_t* __res
   if constexpr (sizeof(TO) == 2) y[(long)n * C + c] = f2bf(s / (float)HW);
   else y[(long)n * C + c] = s / (float)HW;
 }
-template <typename TI>
-__global__ __launch_bounds__(256) void global_avg_bwd_kernel(const TI* __restrict__ dy, bf16_t* __restrict__ dx, int N,
-                                                             int HW, int C) {
-  const long total = (long)N * HW * C;
-  const float inv = 1.f / (float)HW;
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    int c = i % C;
-    long n = i / ((long)HW * C);
-    float g;
-    if constexpr (sizeof(TI) == 2) g = bf2f(dy[n * C + c]);
-    else g = dy[n * C + c];
-    dx[i] = f2bf(g * inv);
-  }
-}
 
-// The same two with 8 channels per lane (C % 8 == 0).  Forward: a block is one image and 512 channels, its four
-// waves split the H*W rows (16-B loads, four in flight per lane) and combine through LDS in a fixed order (the
+// The same with 8 channels per lane (C % 8 == 0): a block is one image and 512 channels, its four waves split the
+// H*W rows (16-B loads, four in flight per lane) and combine through LDS in a fixed order (the
 // one-lane-per-channel form ran H*W dependent 2-B loads per lane: 17.6 us for Inception's 8x8x2048 logits pool).
-// Backward: one lane per 8-channel output chunk, 32-bit magic-number indexing, no grid-stride loop (the form above
-// spent its time in 64-bit divisions: 27 us Inception / 40 us ResNet-50 for a write of 17 / 51 MB).
 template <typename TO>
 __global__ __launch_bounds__(256) void global_avg_fwd8_kernel(const bf16_t* __restrict__ x, TO* __restrict__ y, int HW,
                                                               int C) {
@@ -382,16 +377,9 @@ __global__ __launch_bounds__(256) void global_avg_fwd8_kernel(const bf16_t* __re
 #pragma unroll
       for (int k = 0; k < 4; ++k) u[k] = *(const uint4*)(p + (long)(i + 4 * k) * C);
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        acc[0] += lo_bf(u[k].x); acc[1] += hi_bf(u[k].x); acc[2] += lo_bf(u[k].y); acc[3] += hi_bf(u[k].y);
-        acc[4] += lo_bf(u[k].z); acc[5] += hi_bf(u[k].z); acc[6] += lo_bf(u[k].w); acc[7] += hi_bf(u[k].w);
-      }
+      for (int k = 0; k < 4; ++k) add8(acc, u[k]);
     }
-    for (; i < HW; i += 4) {
-      const uint4 u = *(const uint4*)(p + (long)i * C);
-      acc[0] += lo_bf(u.x); acc[1] += hi_bf(u.x); acc[2] += lo_bf(u.y); acc[3] += hi_bf(u.y);
-      acc[4] += lo_bf(u.z); acc[5] += hi_bf(u.z); acc[6] += lo_bf(u.w); acc[7] += hi_bf(u.w);
-    }
+    for (; i < HW; i += 4) add8(acc, *(const uint4*)(p + (long)i * C));
   }
   if (wv) {
 #pragma unroll
@@ -410,71 +398,11 @@ __global__ __launch_bounds__(256) void global_avg_fwd8_kernel(const bf16_t* __re
     q[1] = make_float4(o[4], o[5], o[6], o[7]);
   }
 }
-template <typename TI>
-__global__ __launch_bounds__(256) void global_avg_bwd8_kernel(const TI* __restrict__ dy, bf16_t* __restrict__ dx, int C,
-                                                              FastDiv fcols, FastDiv fHW, int total, float inv) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= total) return;
-  const uint32_t o = fdiv(i, fcols);  // pixel n*HW + hw
-  const int cv = (int)(i - o * fcols.d) * 8;
-  const int n = (int)fdiv(o, fHW);
-  float g[8];
-  if constexpr (sizeof(TI) == 2) {
-    ld<8>((const bf16_t*)dy + (long)n * C + cv, g);
-  } else {
-    const float4* q = (const float4*)((const float*)dy + (long)n * C + cv);
-    const float4 a = q[0], b = q[1];
-    g[0] = a.x; g[1] = a.y; g[2] = a.z; g[3] = a.w; g[4] = b.x; g[5] = b.y; g[6] = b.z; g[7] = b.w;
-  }
-#pragma unroll
-  for (int e = 0; e < 8; ++e) g[e] *= inv;
-  st<8>(dx + (long)o * C + cv, g);
-}
 
-// ---- BatchNorm-apply + ReLU fused into a max pool (ResNet stem: conv1 -> BN -> ReLU -> 3x3/2 pool) ----
-// The normalised activation relu(x*scale + shift) is formed on the fly from the raw conv output and
-// never stored.  Backward: each input pixel gathers the gradient of the windows whose argmax it is,
-// applies the ReLU mask (recomputed from x) and the BN scale, and accumulates the BN parameter-gradient
-// partial sums (sum g*x, sum g) per block (reduced by reduce_rows), exactly as bn_apply_bwd does.
-__global__ __launch_bounds__(256) void maxpool_bnrelu_fwd_kernel(const bf16_t* __restrict__ x, const float* __restrict__ ss,
-                                                                 bf16_t* __restrict__ y, uint8_t* __restrict__ arg,
-                                                                 PoolArgs a, FastDiv fd_cols, FastDiv fd_Q, FastDiv fd_P) {
-  const uint32_t cols = a.C >> 3, total = (uint32_t)a.N * a.P * a.Q * cols;
-  for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
-    const uint32_t o = fdiv(i, fd_cols), cv = (i - o * cols) * 8;
-    const uint32_t t = fdiv(o, fd_Q), q = o - t * a.Q;
-    const uint32_t n = fdiv(t, fd_P), p = t - n * a.P;
-    float sc[8], sh[8], best[8];
-    uint32_t bi[8];
-    {
-      const float4 s0 = *(const float4*)(ss + cv), s1 = *(const float4*)(ss + cv + 4);
-      const float4 h0 = *(const float4*)(ss + a.C + cv), h1 = *(const float4*)(ss + a.C + cv + 4);
-      sc[0] = s0.x; sc[1] = s0.y; sc[2] = s0.z; sc[3] = s0.w; sc[4] = s1.x; sc[5] = s1.y; sc[6] = s1.z; sc[7] = s1.w;
-      sh[0] = h0.x; sh[1] = h0.y; sh[2] = h0.z; sh[3] = h0.w; sh[4] = h1.x; sh[5] = h1.y; sh[6] = h1.z; sh[7] = h1.w;
-    }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { best[e] = -INFINITY; bi[e] = 0; }
-    for (int r = 0; r < a.KH; ++r) {
-      const int h = (int)p * a.SH - a.PH + r;
-      if (h < 0 || h >= a.H) continue;
-      for (int s = 0; s < a.KW; ++s) {
-        const int w = (int)q * a.SW - a.PW + s;
-        if (w < 0 || w >= a.W) continue;
-        float f[8];
-        ld<8>(x + (((size_t)n * a.H + h) * a.W + w) * a.C + cv, f);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float v = fmaxf(fmaf(f[e], sc[e], sh[e]), 0.f);
-          if (v > best[e]) { best[e] = v; bi[e] = (uint32_t)(r * a.KW + s); }
-        }
-      }
-    }
-    st<8>(y + (size_t)o * a.C + cv, best);
-    *(uint2*)(arg + (size_t)o * a.C + cv) = make_uint2(bi[0] | bi[1] << 8 | bi[2] << 16 | bi[3] << 24,
-                                                      bi[4] | bi[5] << 8 | bi[6] << 16 | bi[7] << 24);
-  }
-}
-
+// ---- BatchNorm-apply + ReLU fused into a max pool, backward (forward: maxpool_fwd_kernel<8, true>): each input
+// pixel gathers the gradient of the windows whose argmax it is, applies the ReLU mask (recomputed from x) and the
+// BN scale, and accumulates the BN parameter-gradient partial sums (sum g*x, sum g) per block (reduced by
+// reduce_rows), exactly as bn_apply_bwd does. ----
 // WM = max windows covering one input pixel per dimension (ceil(k / stride)); all candidate window
 // loads of FU rows are issued before any is consumed (predicated, no data-dependent branches).
 template <int WM, int FU>
@@ -530,17 +458,13 @@ __global__ __launch_bounds__(256) void maxpool_bnrelu_bwd_kernel(const bf16_t* _
 #pragma unroll
       for (int k = 0; k < WM * WM; ++k) {
         float g[8];
-        g[0] = lo_bf(gv[u][k].x); g[1] = hi_bf(gv[u][k].x); g[2] = lo_bf(gv[u][k].y); g[3] = hi_bf(gv[u][k].y);
-        g[4] = lo_bf(gv[u][k].z); g[5] = hi_bf(gv[u][k].z); g[6] = lo_bf(gv[u][k].w); g[7] = hi_bf(gv[u][k].w);
+        unpack8(gv[u][k], g);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const uint32_t b = ((e < 4 ? av[u][k].x : av[u][k].y) >> (8 * (e & 3))) & 0xffu;
-          if (b == want[u][k]) acc[e] += g[e];
-        }
+        for (int e = 0; e < 8; ++e)
+          if (arg_byte(av[u][k], e) == want[u][k]) acc[e] += g[e];
       }
       float xv[8], d[8];
-      xv[0] = lo_bf(xvv[u].x); xv[1] = hi_bf(xvv[u].x); xv[2] = lo_bf(xvv[u].y); xv[3] = hi_bf(xvv[u].y);
-      xv[4] = lo_bf(xvv[u].z); xv[5] = hi_bf(xvv[u].z); xv[6] = lo_bf(xvv[u].w); xv[7] = hi_bf(xvv[u].w);
+      unpack8(xvv[u], xv);
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         const float g = fmaf(xv[e], sc[e], sh[e]) > 0.f ? acc[e] : 0.f;
@@ -560,25 +484,19 @@ __global__ __launch_bounds__(256) void maxpool_bnrelu_bwd_kernel(const bf16_t* _
 // Forward: one lane = two vertically adjacent outputs (p, p + 1) of one 8-channel column: their windows share an
 // input row, so 15 16-B loads (5 rows x 3 columns) instead of 18, all issued before any is used (compile-time
 // window, predicated: an out-of-range tap reads a zero chunk and is never selected).  Same scan order and strict
-// comparison as maxpool_bnrelu_fwd_kernel / maxpool_fwd_kernel: the same maxima and first-maximum argmax bytes.
+// comparison as maxpool_fwd_kernel: the same maxima and first-maximum argmax bytes.
 template <bool BN>
 __global__ __launch_bounds__(256) void maxpool_bnrelu_fwd_k3s2_kernel(const bf16_t* __restrict__ x,
                                                                       const float* __restrict__ ss,
                                                                       bf16_t* __restrict__ y, uint8_t* __restrict__ arg,
-                                                                      PoolArgs a, FastDiv fd_cols, FastDiv fd_Q,
-                                                                      FastDiv fd_P2, const bf16_t* __restrict__ zero) {
+                                                                      PoolArgs a, Idx32 fd_cols, Idx32 fd_Q,
+                                                                      Idx32 fd_P2, const bf16_t* __restrict__ zero) {
   const uint32_t cols = a.C >> 3, P2 = (a.P + 1) >> 1, total = (uint32_t)a.N * P2 * a.Q * cols;
   for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
-    const uint32_t o = fdiv(i, fd_cols), cv = (i - o * cols) * 8;
-    const uint32_t t = fdiv(o, fd_Q), q = o - t * a.Q;
-    const uint32_t n = fdiv(t, fd_P2), p0 = (t - n * P2) * 2;
+    const Split<Idx32> k = split<8>(i, fd_cols, fd_Q, fd_P2);
+    const uint32_t n = k.n, p0 = (uint32_t)k.row * 2, q = (uint32_t)k.col, cv = (uint32_t)k.cv;
     float sc[8], sh[8];
-    if constexpr (BN) {
-      const float4 s0 = *(const float4*)(ss + cv), s1 = *(const float4*)(ss + cv + 4);
-      const float4 h0 = *(const float4*)(ss + a.C + cv), h1 = *(const float4*)(ss + a.C + cv + 4);
-      sc[0] = s0.x; sc[1] = s0.y; sc[2] = s0.z; sc[3] = s0.w; sc[4] = s1.x; sc[5] = s1.y; sc[6] = s1.z; sc[7] = s1.w;
-      sh[0] = h0.x; sh[1] = h0.y; sh[2] = h0.z; sh[3] = h0.w; sh[4] = h1.x; sh[5] = h1.y; sh[6] = h1.z; sh[7] = h1.w;
-    }
+    if constexpr (BN) load_ss8(ss, a.C, cv, sc, sh);
     const int h0 = (int)p0 * 2 - a.PH, w0 = (int)q * 2 - a.PW;
     uint4 v[5][3];
     bool ok[5][3];
@@ -604,9 +522,8 @@ __global__ __launch_bounds__(256) void maxpool_bnrelu_fwd_k3s2_kernel(const bf16
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
           if (!ok[2 * u + r][c]) continue;
-          const uint4 w4 = v[2 * u + r][c];
-          const float f[8] = {lo_bf(w4.x), hi_bf(w4.x), lo_bf(w4.y), hi_bf(w4.y),
-                              lo_bf(w4.z), hi_bf(w4.z), lo_bf(w4.w), hi_bf(w4.w)};
+          float f[8];
+          unpack8(v[2 * u + r][c], f);
 #pragma unroll
           for (int e = 0; e < 8; ++e) {
             const float val = BN ? fmaxf(fmaf(f[e], sc[e], sh[e]), 0.f) : f[e];
@@ -616,8 +533,7 @@ __global__ __launch_bounds__(256) void maxpool_bnrelu_fwd_k3s2_kernel(const bf16
       }
       const size_t oo = (((size_t)n * a.P + p) * a.Q + q) * a.C + cv;
       st<8>(y + oo, best);
-      *(uint2*)(arg + oo) = make_uint2(bi[0] | bi[1] << 8 | bi[2] << 16 | bi[3] << 24,
-                                       bi[4] | bi[5] << 8 | bi[6] << 16 | bi[7] << 24);
+      *(uint2*)(arg + oo) = pack_arg8(bi);
     }
   }
 }
@@ -696,21 +612,17 @@ __global__ __launch_bounds__(256) void maxpool_bnrelu_bwd_k3s2_kernel(const bf16
             const int r = di + 2 * (1 - i), sidx = dj + 2 * (1 - j);
             if (!wv[i][j] || r > 2 || sidx > 2) continue;
             const uint32_t want = (uint32_t)(r * 3 + sidx);
-            const uint4 g4 = gv[i][j];
-            const float g[8] = {lo_bf(g4.x), hi_bf(g4.x), lo_bf(g4.y), hi_bf(g4.y),
-                                lo_bf(g4.z), hi_bf(g4.z), lo_bf(g4.w), hi_bf(g4.w)};
+            float g[8];
+            unpack8(gv[i][j], g);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) {
-              const uint32_t b = ((e < 4 ? av[i][j].x : av[i][j].y) >> (8 * (e & 3))) & 0xffu;
-              if (b == want) acc[e] += g[e];
-            }
+            for (int e = 0; e < 8; ++e)
+              if (arg_byte(av[i][j], e) == want) acc[e] += g[e];
           }
         }
         float d[8];
         if constexpr (BN) {
-          const uint4 x4 = xv[di][dj];
-          const float xf[8] = {lo_bf(x4.x), hi_bf(x4.x), lo_bf(x4.y), hi_bf(x4.y),
-                               lo_bf(x4.z), hi_bf(x4.z), lo_bf(x4.w), hi_bf(x4.w)};
+          float xf[8];
+          unpack8(xv[di][dj], xf);
 #pragma unroll
           for (int e = 0; e < 8; ++e) {
             const float g = fmaf(xf[e], sc[e], sh[e]) > 0.f ? acc[e] : 0.f;
@@ -740,13 +652,12 @@ __global__ __launch_bounds__(256) void maxpool_bnrelu_bwd_k3s2_kernel(const bf16
 // adds its taps (windows) in the generic kernels' order with their divisors: bit-identical results.
 constexpr int AVG_R = 4;
 __global__ __launch_bounds__(256) void avgpool_fwd_k3s1_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ y,
-                                                               PoolArgs a, int count_pad, FastDiv fd_cols, FastDiv fd_Q,
-                                                               FastDiv fd_PR, const bf16_t* __restrict__ zero) {
+                                                               PoolArgs a, int count_pad, Idx32 fd_cols, Idx32 fd_Q,
+                                                               Idx32 fd_PR, const bf16_t* __restrict__ zero) {
   const uint32_t cols = a.C >> 3, PR = (a.P + AVG_R - 1) / AVG_R, total = (uint32_t)a.N * PR * a.Q * cols;
   for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
-    const uint32_t o = fdiv(i, fd_cols), cv = (i - o * cols) * 8;
-    const uint32_t t = fdiv(o, fd_Q), q = o - t * a.Q;
-    const uint32_t n = fdiv(t, fd_PR), p0 = (t - n * PR) * AVG_R;
+    const Split<Idx32> k = split<8>(i, fd_cols, fd_Q, fd_PR);
+    const uint32_t n = k.n, p0 = (uint32_t)k.row * AVG_R, q = (uint32_t)k.col, cv = (uint32_t)k.cv;
     const int h0 = (int)p0 - a.PH, w0 = (int)q - a.PW;
     uint4 v[AVG_R + 2][3];
     bool ok[AVG_R + 2][3];
@@ -772,11 +683,7 @@ __global__ __launch_bounds__(256) void avgpool_fwd_k3s1_kernel(const bf16_t* __r
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
           if (!ok[u + r][c]) continue;
-          const uint4 w4 = v[u + r][c];
-          const float f[8] = {lo_bf(w4.x), hi_bf(w4.x), lo_bf(w4.y), hi_bf(w4.y),
-                              lo_bf(w4.z), hi_bf(w4.z), lo_bf(w4.w), hi_bf(w4.w)};
-#pragma unroll
-          for (int e = 0; e < 8; ++e) acc[e] += f[e];
+          add8(acc, v[u + r][c]);
           ++cnt;
         }
       }
@@ -789,13 +696,12 @@ __global__ __launch_bounds__(256) void avgpool_fwd_k3s1_kernel(const bf16_t* __r
 }
 
 __global__ __launch_bounds__(256) void avgpool_bwd_k3s1_kernel(const bf16_t* __restrict__ dy, bf16_t* __restrict__ dx,
-                                                               PoolArgs a, int count_pad, FastDiv fd_cols, FastDiv fd_W,
-                                                               FastDiv fd_HR, const bf16_t* __restrict__ zero) {
+                                                               PoolArgs a, int count_pad, Idx32 fd_cols, Idx32 fd_W,
+                                                               Idx32 fd_HR, const bf16_t* __restrict__ zero) {
   const uint32_t cols = a.C >> 3, HR = (a.H + AVG_R - 1) / AVG_R, total = (uint32_t)a.N * HR * a.W * cols;
   for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
-    const uint32_t o = fdiv(i, fd_cols), cv = (i - o * cols) * 8;
-    const uint32_t t = fdiv(o, fd_W), w = o - t * a.W;
-    const uint32_t n = fdiv(t, fd_HR), hs = (t - n * HR) * AVG_R;
+    const Split<Idx32> k = split<8>(i, fd_cols, fd_W, fd_HR);
+    const uint32_t n = k.n, hs = (uint32_t)k.row * AVG_R, w = (uint32_t)k.col, cv = (uint32_t)k.cv;
     // windows p covering rows hs .. hs + AVG_R - 1: p = h + PH - 2 .. h + PH (stride 1), i.e. rows pr0 .. pr0 + AVG_R + 1
     const int pr0 = (int)hs + a.PH - 2, qc0 = (int)w + a.PW - 2;
     uint4 g[AVG_R + 2][3];
@@ -826,9 +732,8 @@ __global__ __launch_bounds__(256) void avgpool_bwd_k3s1_kernel(const bf16_t* __r
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
           if (!wv[u + r][c]) continue;
-          const uint4 g4 = g[u + r][c];
-          const float gf[8] = {lo_bf(g4.x), hi_bf(g4.x), lo_bf(g4.y), hi_bf(g4.y),
-                               lo_bf(g4.z), hi_bf(g4.z), lo_bf(g4.w), hi_bf(g4.w)};
+          float gf[8];
+          unpack8(g[u + r][c], gf);
           const float iv = inv[u + r][c];
 #pragma unroll
           for (int e = 0; e < 8; ++e) acc[e] += gf[e] * iv;
@@ -847,145 +752,176 @@ static int pgrid(long work) {
   return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
 }
 
-static int g_pool_k3s2 = 1;  // A/B knob (dtm_pool_set_k3s2): the 3x3 / stride-2 specialised stem-pool kernels
+static int g_pool_k3s2 = 1;  // A/B knob (dtm_pool_set_k3s2): the 3x3 / stride-2 and stride-1 specialised kernels
 DTM_API void dtm_pool_set_k3s2(int on) { g_pool_k3s2 = on; }
-static bool k3s2(const PoolArgs* a) {
-  return g_pool_k3s2 && a->KH == 3 && a->KW == 3 && a->SH == 2 && a->SW == 2 && a->PH >= 0 && a->PH <= 1 &&
-         a->PW >= 0 && a->PW <= 1;
-}
 const void* dtm_zero_chunk();  // >= 16 B of device zeros (conv_igemm.hip)
 
-DTM_API void dtm_maxpool_fwd(const void* x, void* y, void* arg, const PoolArgs* a, void* stream) {
-  long work = (long)a->N * a->P * a->Q * a->C;
-  if (a->C % 8 == 0 && arg && k3s2(a) && (long)a->N * a->H * a->W * a->C < (1l << 31)) {
-    const long w2 = (long)a->N * ((a->P + 1) / 2) * a->Q * (a->C / 8);
-    hipLaunchKernelGGL(maxpool_bnrelu_fwd_k3s2_kernel<false>, dim3(pgrid(w2)), dim3(256), 0, (hipStream_t)stream,
-                       (const bf16_t*)x, (const float*)nullptr, (bf16_t*)y, (uint8_t*)arg, *a, make_fastdiv(a->C / 8),
-                       make_fastdiv(a->Q), make_fastdiv((a->P + 1) / 2), (const bf16_t*)dtm_zero_chunk());
-    return;
-  }
-  if (a->C % 8 == 0)
-    hipLaunchKernelGGL(maxpool_fwd_kernel<8>, dim3(pgrid(work / 8)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
-                       (bf16_t*)y, (uint8_t*)arg, *a);
-  else
-    hipLaunchKernelGGL(maxpool_fwd_kernel<1>, dim3(pgrid(work)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
-                       (bf16_t*)y, (uint8_t*)arg, *a);
+// ---- which kernel applies ----
+static bool fits32(const PoolArgs* a) {  // 32-bit indexing: input and output below 2^31 elements
+  return (long)a->N * a->H * a->W * a->C < (1l << 31) && (long)a->N * a->P * a->Q * a->C < (1l << 31);
 }
-static void maxpool_bwd_k3s2(const void* dy, int ldy, const void* arg, void* dx, const PoolArgs* a, void* stream);
-DTM_API void dtm_maxpool_bwd(const void* dy, const void* arg, void* dx, const PoolArgs* a, void* stream) {
-  long work = (long)a->N * a->H * a->W * a->C;
-  if (a->C % 8 == 0 && a->C / 8 <= 256 && k3s2(a) && (long)a->N * a->H * a->W * a->C < (1l << 31)) {
-    maxpool_bwd_k3s2(dy, a->C, arg, dx, a, stream);
+static bool k3pad01(const PoolArgs* a, int stride) {
+  return g_pool_k3s2 && a->KH == 3 && a->KW == 3 && a->SH == stride && a->SW == stride && a->PH >= 0 && a->PH <= 1 &&
+         a->PW >= 0 && a->PW <= 1 && a->C % 8 == 0 && fits32(a);
+}
+static bool k3s2_ok(const PoolArgs* a) { return k3pad01(a, 2); }
+static bool k3s1_ok(const PoolArgs* a) { return k3pad01(a, 1); }
+static bool valid53(const PoolArgs* a) {  // the 5x5/3 VALID pool with every window in bounds (aux head), 8-channel lanes
+  return a->KH == 5 && a->KW == 5 && a->SH == 3 && a->SW == 3 && a->PH == 0 && a->PW == 0 &&
+         (a->P - 1) * 3 + 5 <= a->H && (a->Q - 1) * 3 + 5 <= a->W && a->C % 8 == 0 && fits32(a);
+}
+// The instance of a generic body for these sizes: FN<V, Index>(args...)
+#define POOL_GENERIC(a, FN, ...)                                       \
+  do {                                                                 \
+    if ((a)->C % 8) FN<1, Idx64>(__VA_ARGS__);                         \
+    else if (fits32(a)) FN<8, Idx32>(__VA_ARGS__);                     \
+    else FN<8, Idx64>(__VA_ARGS__);                                    \
+  } while (0)
+
+// Column-fixed lane mapping of the BN backward kernels (a block = 256 / cols row-lanes x cols 8-channel columns):
+// blocks of about `lanes` row-chunks each, at most 2048, every block a whole number of row-lane rounds (*rpb rows).
+static int row_blocks(long rows, int cols, int lanes, int* rpb) {
+  const int RP = 256 / cols;
+  long b = rows * cols / lanes;
+  if (b < 1) b = 1;
+  if (b > 2048) b = 2048;
+  long r = (rows + b - 1) / b;
+  r = (r + RP - 1) / RP * RP;
+  *rpb = (int)r;
+  return (int)((rows + r - 1) / r);
+}
+
+// ---- launch wrappers of the generic bodies ----
+template <int V, class Index, bool BN = false>
+static void launch_maxpool_fwd(const void* x, const float* ss, void* y, void* arg, const PoolArgs* a, void* stream) {
+  const long total = (long)a->N * a->P * a->Q * (a->C / V);
+  hipLaunchKernelGGL((maxpool_fwd_kernel<V, BN, Index>), dim3(pgrid(total)), dim3(256), 0, (hipStream_t)stream,
+                     (const bf16_t*)x, ss, (bf16_t*)y, (uint8_t*)arg, *a, Index::make(a->C / V), Index::make(a->Q),
+                     Index::make(a->P), (typename Index::T)total);
+}
+template <int V, class Index>
+static void launch_maxpool_bwd(const void* dy, const void* arg, void* dx, const PoolArgs* a, void* stream) {
+  const long total = (long)a->N * a->H * a->W * (a->C / V);
+  hipLaunchKernelGGL((maxpool_bwd_kernel<V, Index>), dim3(pgrid(total)), dim3(256), 0, (hipStream_t)stream,
+                     (const bf16_t*)dy, (const uint8_t*)arg, (bf16_t*)dx, *a, Index::make(a->C / V), Index::make(a->W),
+                     Index::make(a->H), (typename Index::T)total);
+}
+template <int V, class Index>
+static void launch_avgpool_fwd(const void* x, void* y, const PoolArgs* a, int count_pad, void* stream) {
+  const long total = (long)a->N * a->P * a->Q * (a->C / V);
+  hipLaunchKernelGGL((avgpool_fwd_kernel<V, Index>), dim3(pgrid(total)), dim3(256), 0, (hipStream_t)stream,
+                     (const bf16_t*)x, (bf16_t*)y, *a, count_pad, Index::make(a->C / V), Index::make(a->Q),
+                     Index::make(a->P), (typename Index::T)total);
+}
+template <int V, class Index>
+static void launch_avgpool_bwd(const void* dy, void* dx, const PoolArgs* a, int count_pad, int accum, void* stream) {
+  const long total = (long)a->N * a->H * a->W * (a->C / V);
+  hipLaunchKernelGGL((avgpool_bwd_kernel<V, Index>), dim3(pgrid(total)), dim3(256), 0, (hipStream_t)stream,
+                     (const bf16_t*)dy, (bf16_t*)dx, *a, count_pad, accum, Index::make(a->C / V), Index::make(a->W),
+                     Index::make(a->H), (typename Index::T)total);
+}
+template <int V, class Index, typename TI>
+static void launch_global_avg_bwd(const TI* dy, void* dx, int N, int HW, int C, void* stream) {
+  const long total = (long)N * HW * (C / V);
+  hipLaunchKernelGGL((global_avg_bwd_kernel<TI, V, Index>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
+                     (hipStream_t)stream, dy, (bf16_t*)dx, C, Index::make(C / V), Index::make(HW),
+                     (typename Index::T)total, 1.f / (float)HW);
+}
+
+// ---- max pool ----
+DTM_API void dtm_maxpool_fwd(const void* x, void* y, void* arg, const PoolArgs* a, void* stream) {
+  if (arg && k3s2_ok(a)) {
+    const int P2 = (a->P + 1) / 2;
+    hipLaunchKernelGGL(maxpool_bnrelu_fwd_k3s2_kernel<false>, dim3(pgrid((long)a->N * P2 * a->Q * (a->C / 8))), dim3(256),
+                       0, (hipStream_t)stream, (const bf16_t*)x, (const float*)nullptr, (bf16_t*)y, (uint8_t*)arg, *a,
+                       Idx32::make(a->C / 8), Idx32::make(a->Q), Idx32::make(P2), (const bf16_t*)dtm_zero_chunk());
     return;
   }
-  if (a->C % 8 == 0)
-    hipLaunchKernelGGL(maxpool_bwd_kernel<8>, dim3(pgrid(work / 8)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dy,
-                       (const uint8_t*)arg, (bf16_t*)dx, *a);
-  else
-    hipLaunchKernelGGL(maxpool_bwd_kernel<1>, dim3(pgrid(work)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dy,
-                       (const uint8_t*)arg, (bf16_t*)dx, *a);
+  POOL_GENERIC(a, launch_maxpool_fwd, x, nullptr, y, arg, a, stream);
+}
+// The 3x3 / stride-2 backward (one row = a 2 x 2 block of input pixels): the plain max-pool gradient (BN = false:
+// no x, ss, sums), or with BN-apply backward and its parameter-gradient sums (per-block partials in the stream's
+// workspace, reduced into sums).  Needs k3s2_ok(a) and C / 8 <= 256.
+template <bool BN>
+static int launch_maxpool_bwd_k3s2(const void* dy, int ldy, const void* arg, const void* x, const float* ss, void* dx,
+                                   float* sums, const PoolArgs* a, int unscaled, void* stream) {
+  const int BH = (a->H + a->PH + 1) / 2, BW = (a->W + a->PW + 1) / 2;
+  int rpb;
+  const int blocks = row_blocks((long)a->N * BH * BW, a->C / 8, 256 * 2, &rpb);
+  float* ws = nullptr;
+  if (BN && !(ws = dtm_ws_get_stream((size_t)blocks * 2 * a->C, (hipStream_t)stream))) return -4;
+  hipLaunchKernelGGL(maxpool_bnrelu_bwd_k3s2_kernel<BN>, dim3(blocks), dim3(256), 0, (hipStream_t)stream,
+                     (const bf16_t*)dy, (const uint8_t*)arg, (const bf16_t*)x, ss, (bf16_t*)dx, ws, *a, make_fastdiv(BW),
+                     make_fastdiv(BH), unscaled, rpb, (const bf16_t*)dtm_zero_chunk(), ldy);
+  if (BN) dtm_reduce_rows(ws, blocks, 2 * a->C, 2 * a->C, sums, (hipStream_t)stream);
+  return 0;
+}
+DTM_API void dtm_maxpool_bwd(const void* dy, const void* arg, void* dx, const PoolArgs* a, void* stream) {
+  if (k3s2_ok(a) && a->C / 8 <= 256) {
+    launch_maxpool_bwd_k3s2<false>(dy, a->C, arg, nullptr, nullptr, dx, nullptr, a, 0, stream);
+    return;
+  }
+  POOL_GENERIC(a, launch_maxpool_bwd, dy, arg, dx, a, stream);
 }
 // dy read in place with a pixel pitch of ldy elements (the max-pool branch's slice of a concat gradient): 3x3 / stride 2
 // only (-1 otherwise: the caller makes dy contiguous)
 DTM_API int dtm_maxpool_bwd_ld(const void* dy, int ldy, const void* arg, void* dx, const PoolArgs* a, void* stream) {
-  if (!(a->C % 8 == 0 && a->C / 8 <= 256 && k3s2(a) && (long)a->N * a->H * a->W * a->C < (1l << 31)) || ldy < a->C ||
-      ldy % 8 || ((uintptr_t)dy & 15) || (long)a->N * a->P * a->Q * ldy >= (1l << 31))
+  if (!(k3s2_ok(a) && a->C / 8 <= 256) || ldy < a->C || ldy % 8 || ((uintptr_t)dy & 15) ||
+      (long)a->N * a->P * a->Q * ldy >= (1l << 31))
     return -1;
-  maxpool_bwd_k3s2(dy, ldy, arg, dx, a, stream);
-  return 0;
+  return launch_maxpool_bwd_k3s2<false>(dy, ldy, arg, nullptr, nullptr, dx, nullptr, a, 0, stream);
 }
-static void maxpool_bwd_k3s2(const void* dy, int ldy, const void* arg, void* dx, const PoolArgs* a, void* stream) {
-  const int cols = a->C / 8, RP = 256 / cols;  // (the BN kernel's row mapping: one row = a 2 x 2 pixel block)
-  const int BH = (a->H + a->PH + 1) / 2, BW = (a->W + a->PW + 1) / 2;
-  const long MB = (long)a->N * BH * BW;
-  long b = MB * cols / (256 * 2);
-  if (b < 1) b = 1;
-  if (b > 2048) b = 2048;
-  long rpb = (MB + b - 1) / b;
-  rpb = (rpb + RP - 1) / RP * RP;
-  const int blocks = (int)((MB + rpb - 1) / rpb);
-  hipLaunchKernelGGL(maxpool_bnrelu_bwd_k3s2_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream,
-                     (const bf16_t*)dy, (const uint8_t*)arg, (const bf16_t*)nullptr, (const float*)nullptr,
-                     (bf16_t*)dx, (float*)nullptr, *a, make_fastdiv(BW), make_fastdiv(BH), 0, (int)rpb,
-                     (const bf16_t*)dtm_zero_chunk(), ldy);
-}
-static bool k3s1(const PoolArgs* a) {
-  return g_pool_k3s2 && a->KH == 3 && a->KW == 3 && a->SH == 1 && a->SW == 1 && a->PH >= 0 && a->PH <= 1 &&
-         a->PW >= 0 && a->PW <= 1 && a->C % 8 == 0 && (long)a->N * a->H * a->W * a->C < (1l << 31);
-}
-static bool avg8(const PoolArgs* a) {  // the 32-bit-index 8-channel kernels apply
-  return a->C % 8 == 0 && (long)a->N * a->H * a->W * a->C < (1l << 31) && (long)a->N * a->P * a->Q * a->C < (1l << 31);
-}
-static bool valid53(const PoolArgs* a) {  // the 5x5/3 VALID pool with every window in bounds (aux head)
-  return a->KH == 5 && a->KW == 5 && a->SH == 3 && a->SW == 3 && a->PH == 0 && a->PW == 0 &&
-         (a->P - 1) * 3 + 5 <= a->H && (a->Q - 1) * 3 + 5 <= a->W;
-}
-static void avgpool_bwd8(const void* dy, void* dx, const PoolArgs* a, int count_pad, int accum, void* stream) {
-  const long work = (long)a->N * a->H * a->W * a->C;
+
+// ---- avg pool ----
+static void avgpool_bwd(const void* dy, void* dx, const PoolArgs* a, int count_pad, int accum, void* stream) {
   if (valid53(a)) {
-    hipLaunchKernelGGL((avgpool_bwd_valid_kernel<5, 3>), dim3((unsigned)((work / 8 + 255) / 256)), dim3(256), 0,
-                       (hipStream_t)stream, (const bf16_t*)dy, (bf16_t*)dx, *a, accum, make_fastdiv(a->C / 8),
-                       make_fastdiv(a->W), make_fastdiv(a->H), (int)(work / 8), (const bf16_t*)dtm_zero_chunk());
+    const long total = (long)a->N * a->H * a->W * (a->C / 8);
+    hipLaunchKernelGGL((avgpool_bwd_valid_kernel<5, 3>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
+                       (hipStream_t)stream, (const bf16_t*)dy, (bf16_t*)dx, *a, accum, Idx32::make(a->C / 8),
+                       Idx32::make(a->W), Idx32::make(a->H), (int)total, (const bf16_t*)dtm_zero_chunk());
     return;
   }
-  hipLaunchKernelGGL(avgpool_bwd8_kernel, dim3(pgrid(work / 8)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dy,
-                     (bf16_t*)dx, *a, count_pad, accum, make_fastdiv(a->C / 8), make_fastdiv(a->W), make_fastdiv(a->H),
-                     (int)(work / 8));
+  POOL_GENERIC(a, launch_avgpool_bwd, dy, dx, a, count_pad, accum, stream);
 }
-// dx += avgpool_bwd(dy) (-1 when the 8-channel kernel does not apply: the caller adds itself)
+// dx += avgpool_bwd(dy) (-1 when the 8-channel 32-bit kernels do not apply: the caller adds itself)
 DTM_API int dtm_avgpool_bwd_acc(const void* dy, void* dx, const PoolArgs* a, int count_pad, void* stream) {
-  if (!avg8(a) || ((uintptr_t)dy & 15) || ((uintptr_t)dx & 15)) return -1;
-  avgpool_bwd8(dy, dx, a, count_pad, 1, stream);
+  if (a->C % 8 || !fits32(a) || ((uintptr_t)dy & 15) || ((uintptr_t)dx & 15)) return -1;
+  avgpool_bwd(dy, dx, a, count_pad, 1, stream);
   return 0;
 }
 DTM_API void dtm_avgpool_fwd(const void* x, void* y, const PoolArgs* a, int count_pad, void* stream) {
-  long work = (long)a->N * a->P * a->Q * a->C;
-  if (k3s1(a)) {
+  if (k3s1_ok(a)) {
     const int PR = (a->P + AVG_R - 1) / AVG_R;
     hipLaunchKernelGGL(avgpool_fwd_k3s1_kernel, dim3(pgrid((long)a->N * PR * a->Q * (a->C / 8))), dim3(256), 0,
-                       (hipStream_t)stream, (const bf16_t*)x, (bf16_t*)y, *a, count_pad, make_fastdiv(a->C / 8),
-                       make_fastdiv(a->Q), make_fastdiv(PR), (const bf16_t*)dtm_zero_chunk());
+                       (hipStream_t)stream, (const bf16_t*)x, (bf16_t*)y, *a, count_pad, Idx32::make(a->C / 8),
+                       Idx32::make(a->Q), Idx32::make(PR), (const bf16_t*)dtm_zero_chunk());
     return;
   }
-  if (avg8(a) && valid53(a))
-    hipLaunchKernelGGL(avgpool_fwd_valid_kernel<5>, dim3((unsigned)((work / 8 + 255) / 256)), dim3(256), 0,
-                       (hipStream_t)stream, (const bf16_t*)x, (bf16_t*)y, *a, make_fastdiv(a->C / 8),
-                       make_fastdiv(a->Q), make_fastdiv(a->P), (int)(work / 8));
-  else if (avg8(a))
-    hipLaunchKernelGGL(avgpool_fwd8_kernel, dim3(pgrid(work / 8)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
-                       (bf16_t*)y, *a, count_pad, make_fastdiv(a->C / 8), make_fastdiv(a->Q), make_fastdiv(a->P),
-                       (int)(work / 8));
-  else if (a->C % 8 == 0)
-    hipLaunchKernelGGL(avgpool_fwd_kernel<8>, dim3(pgrid(work / 8)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
-                       (bf16_t*)y, *a, count_pad);
-  else
-    hipLaunchKernelGGL(avgpool_fwd_kernel<1>, dim3(pgrid(work)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
-                       (bf16_t*)y, *a, count_pad);
+  if (valid53(a)) {
+    const long total = (long)a->N * a->P * a->Q * (a->C / 8);
+    hipLaunchKernelGGL(avgpool_fwd_valid_kernel<5>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
+                       (hipStream_t)stream, (const bf16_t*)x, (bf16_t*)y, *a, Idx32::make(a->C / 8), Idx32::make(a->Q),
+                       Idx32::make(a->P), (int)total);
+    return;
+  }
+  POOL_GENERIC(a, launch_avgpool_fwd, x, y, a, count_pad, stream);
 }
 DTM_API void dtm_avgpool_bwd(const void* dy, void* dx, const PoolArgs* a, int count_pad, void* stream) {
-  long work = (long)a->N * a->H * a->W * a->C;
-  if (k3s1(a)) {
+  if (k3s1_ok(a)) {
     const int HR = (a->H + AVG_R - 1) / AVG_R;
     hipLaunchKernelGGL(avgpool_bwd_k3s1_kernel, dim3(pgrid((long)a->N * HR * a->W * (a->C / 8))), dim3(256), 0,
-                       (hipStream_t)stream, (const bf16_t*)dy, (bf16_t*)dx, *a, count_pad, make_fastdiv(a->C / 8),
-                       make_fastdiv(a->W), make_fastdiv(HR), (const bf16_t*)dtm_zero_chunk());
+                       (hipStream_t)stream, (const bf16_t*)dy, (bf16_t*)dx, *a, count_pad, Idx32::make(a->C / 8),
+                       Idx32::make(a->W), Idx32::make(HR), (const bf16_t*)dtm_zero_chunk());
     return;
   }
-  if (avg8(a))
-    avgpool_bwd8(dy, dx, a, count_pad, 0, stream);
-  else if (a->C % 8 == 0)
-    hipLaunchKernelGGL(avgpool_bwd_kernel<8>, dim3(pgrid(work / 8)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dy,
-                       (bf16_t*)dx, *a, count_pad);
-  else
-    hipLaunchKernelGGL(avgpool_bwd_kernel<1>, dim3(pgrid(work)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dy,
-                       (bf16_t*)dx, *a, count_pad);
+  avgpool_bwd(dy, dx, a, count_pad, 0, stream);
 }
-static bool gavg8(const void* x, const void* y, long N, long HW, int C) {
-  return C % 8 == 0 && !((uintptr_t)x & 15) && !((uintptr_t)y & 15) && N * HW * C < (1l << 31) && N <= 65535;
-}
+
+// ---- global mean ----
 template <typename TO>
 static void global_avg_fwd(const void* x, TO* y, int N, int HW, int C, void* stream) {
-  if (gavg8(x, y, N, HW, C))
+  const PoolArgs g = {N, HW, 1, C, 1, 1};
+  if (C % 8 == 0 && !((uintptr_t)x & 15) && !((uintptr_t)y & 15) && fits32(&g) && N <= 65535)
     hipLaunchKernelGGL(global_avg_fwd8_kernel<TO>, dim3((C / 8 + 63) / 64, N), dim3(256), 0, (hipStream_t)stream,
                        (const bf16_t*)x, y, HW, C);
   else
@@ -994,14 +930,11 @@ static void global_avg_fwd(const void* x, TO* y, int N, int HW, int C, void* str
 }
 template <typename TI>
 static void global_avg_bwd(const TI* dy, void* dx, int N, int HW, int C, void* stream) {
-  if (gavg8(dy, dx, N, HW, C)) {
-    const int total = N * HW * (C / 8);
-    hipLaunchKernelGGL(global_avg_bwd8_kernel<TI>, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, dy,
-                       (bf16_t*)dx, C, make_fastdiv(C / 8), make_fastdiv(HW), total, 1.f / (float)HW);
-  } else {
-    hipLaunchKernelGGL(global_avg_bwd_kernel<TI>, dim3(pgrid((long)N * HW * C)), dim3(256), 0, (hipStream_t)stream,
-                       dy, (bf16_t*)dx, N, HW, C);
-  }
+  const PoolArgs g = {N, HW, 1, C, 1, 1};
+  if (((uintptr_t)dy & 15) || ((uintptr_t)dx & 15))  // no 16-B accesses: one-channel lanes
+    launch_global_avg_bwd<1, Idx64>(dy, dx, N, HW, C, stream);
+  else
+    POOL_GENERIC(&g, launch_global_avg_bwd, dy, dx, N, HW, C, stream);
 }
 DTM_API void dtm_global_avg_fwd(const void* x, float* y, int N, int HW, int C, void* stream) {
   global_avg_fwd<float>(x, y, N, HW, C, stream);
@@ -1017,63 +950,40 @@ DTM_API void dtm_global_avg_bwd_bf16(const void* dy, void* dx, int N, int HW, in
   global_avg_bwd<bf16_t>((const bf16_t*)dy, dx, N, HW, C, stream);
 }
 
+// ---- BatchNorm-apply + ReLU fused into a max pool ----
 // y = maxpool(relu(x*scale + shift)) with a uint8 argmax per output element (ss = [scale; shift; ...])
 DTM_API int dtm_maxpool_bnrelu_fwd(const void* x, const float* ss, void* y, void* arg, const PoolArgs* a, void* stream) {
-  if (a->C % 8 || a->KH * a->KW > 255 || (long)a->N * a->H * a->W * a->C >= (1l << 31)) return -1;
-  if (k3s2(a)) {
-    const long work = (long)a->N * ((a->P + 1) / 2) * a->Q * (a->C / 8);
-    hipLaunchKernelGGL(maxpool_bnrelu_fwd_k3s2_kernel<true>, dim3(pgrid(work)), dim3(256), 0, (hipStream_t)stream,
-                       (const bf16_t*)x, ss, (bf16_t*)y, (uint8_t*)arg, *a, make_fastdiv(a->C / 8), make_fastdiv(a->Q),
-                       make_fastdiv((a->P + 1) / 2), (const bf16_t*)dtm_zero_chunk());
+  if (a->C % 8 || a->KH * a->KW > 255 || !fits32(a)) return -1;
+  if (k3s2_ok(a)) {
+    const int P2 = (a->P + 1) / 2;
+    hipLaunchKernelGGL(maxpool_bnrelu_fwd_k3s2_kernel<true>, dim3(pgrid((long)a->N * P2 * a->Q * (a->C / 8))), dim3(256),
+                       0, (hipStream_t)stream, (const bf16_t*)x, ss, (bf16_t*)y, (uint8_t*)arg, *a, Idx32::make(a->C / 8),
+                       Idx32::make(a->Q), Idx32::make(P2), (const bf16_t*)dtm_zero_chunk());
     return 0;
   }
-  const long work = (long)a->N * a->P * a->Q * (a->C / 8);
-  hipLaunchKernelGGL(maxpool_bnrelu_fwd_kernel, dim3(pgrid(work)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
-                     ss, (bf16_t*)y, (uint8_t*)arg, *a, make_fastdiv(a->C / 8), make_fastdiv(a->Q), make_fastdiv(a->P));
+  launch_maxpool_fwd<8, Idx32, true>(x, ss, y, arg, a, stream);
   return 0;
 }
 
 // dx = [x*scale+shift > 0] * scale * maxpool_grad(dy);  sums[0..1][C] += (sum g*x, sum g)
 DTM_API int dtm_maxpool_bnrelu_bwd(const void* dy, const void* arg, const void* x, const float* ss, void* dx,
                                    float* sums, const PoolArgs* a, int unscaled, void* stream) {
-  if (a->C % 8 || a->C / 8 > 256 || (long)a->N * a->H * a->W * a->C >= (1l << 31)) return -1;
+  if (a->C % 8 || a->C / 8 > 256 || !fits32(a)) return -1;
   if ((a->KH + a->SH - 1) / a->SH > 3 || (a->KW + a->SW - 1) / a->SW > 3) return -2;
-  const int cols = a->C / 8, RP = 256 / cols;
-  if (k3s2(a)) {  // one row = a 2 x 2 block of input pixels
-    const int BH = (a->H + a->PH + 1) / 2, BW = (a->W + a->PW + 1) / 2;
-    const long MB = (long)a->N * BH * BW;
-    long b = MB * cols / (256 * 2);
-    if (b < 1) b = 1;
-    if (b > 2048) b = 2048;
-    long rpb = (MB + b - 1) / b;
-    rpb = (rpb + RP - 1) / RP * RP;
-    const int blocks = (int)((MB + rpb - 1) / rpb);
-    float* ws = dtm_ws_get_stream((size_t)blocks * 2 * a->C, (hipStream_t)stream);
-    if (!ws) return -4;
-    hipLaunchKernelGGL(maxpool_bnrelu_bwd_k3s2_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream,
-                       (const bf16_t*)dy, (const uint8_t*)arg, (const bf16_t*)x, ss, (bf16_t*)dx, ws, *a,
-                       make_fastdiv(BW), make_fastdiv(BH), unscaled, (int)rpb, (const bf16_t*)dtm_zero_chunk(), a->C);
-    dtm_reduce_rows(ws, blocks, 2 * a->C, 2 * a->C, sums, (hipStream_t)stream);
-    return 0;
-  }
-  const long M = (long)a->N * a->H * a->W;
-  long b = M * cols / (256 * 8);
-  if (b < 1) b = 1;
-  if (b > 2048) b = 2048;
-  long rpb = (M + b - 1) / b;
-  rpb = (rpb + RP - 1) / RP * RP;
-  const int blocks = (int)((M + rpb - 1) / rpb);
+  if (k3s2_ok(a)) return launch_maxpool_bwd_k3s2<true>(dy, a->C, arg, x, ss, dx, sums, a, unscaled, stream);
+  int rpb;
+  const int blocks = row_blocks((long)a->N * a->H * a->W, a->C / 8, 256 * 8, &rpb);
   float* ws = dtm_ws_get_stream((size_t)blocks * 2 * a->C, (hipStream_t)stream);
   if (!ws) return -4;
   const int wm = max((a->KH + a->SH - 1) / a->SH, (a->KW + a->SW - 1) / a->SW);
   if (wm <= 2)
     hipLaunchKernelGGL((maxpool_bnrelu_bwd_kernel<2, 2>), dim3(blocks), dim3(256), 0, (hipStream_t)stream,
                        (const bf16_t*)dy, (const uint8_t*)arg, (const bf16_t*)x, ss, (bf16_t*)dx, ws, *a,
-                       make_fastdiv(a->W), make_fastdiv(a->H), unscaled, (int)rpb);
+                       make_fastdiv(a->W), make_fastdiv(a->H), unscaled, rpb);
   else
     hipLaunchKernelGGL((maxpool_bnrelu_bwd_kernel<3, 1>), dim3(blocks), dim3(256), 0, (hipStream_t)stream,
                        (const bf16_t*)dy, (const uint8_t*)arg, (const bf16_t*)x, ss, (bf16_t*)dx, ws, *a,
-                       make_fastdiv(a->W), make_fastdiv(a->H), unscaled, (int)rpb);
+                       make_fastdiv(a->W), make_fastdiv(a->H), unscaled, rpb);
   dtm_reduce_rows(ws, blocks, 2 * a->C, 2 * a->C, sums, (hipStream_t)stream);
   return 0;
 }

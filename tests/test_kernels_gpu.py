@@ -459,6 +459,70 @@ def test_maxpool_bnrelu_k3s2_matches_generic(case, unscaled):
     assert _rel(out[1][3][1], gref.sum((0, 1, 2))) < 2e-2
 
 
+@pytest.mark.parametrize("k,st,pad", [(3, 2, "SAME"), (2, 2, "VALID"), (3, 1, "SAME"), (5, 3, "VALID")])
+def test_pool_generic_lane_widths_agree(k, st, pad):
+    """The generic pool bodies at both lane widths: a 20-channel tensor (C % 8 != 0: one-channel lanes, 64-bit index
+    policy) against its first 16 channels run on their own (eight-channel lanes, 32-bit policy; the 3x3 specialisations
+    switched off).  Channels are independent and the tap order is the same, so y, argmax bytes and dx are bit-identical;
+    and the 20-channel results against fp32 torch.  No other test feeds a pool a channel count that is not a multiple
+    of 8, so this is the one that runs the one-channel bodies and the 64-bit index policy."""
+    import ctypes
+
+    import torch.nn.functional as tF
+
+    from distributed_tensorflow_models_amd.ops import _lib
+    from distributed_tensorflow_models_amd.ops.geometry import pool_geom
+    torch.manual_seed(11)
+    L = _lib.lib()
+    s = _lib.stream_ptr()
+    x20 = torch.randn(2, 11, 10, 20, device=DEV).to(torch.bfloat16)
+    g = pool_geom(tuple(x20.shape), k, st, pad)
+    dy20 = torch.randn(2, g.P, g.Q, 20, device=DEV).to(torch.bfloat16)
+
+    def run(x, dy, generic):
+        a = pool_geom(tuple(x.shape), k, st, pad).as_args(_lib.PoolArgs)
+        out = {}
+        if generic:
+            L.dtm_pool_set_k3s2(0)
+        try:
+            out["y"], out["dx"] = torch.empty_like(dy), torch.empty_like(x)
+            out["arg"] = torch.empty_like(dy, dtype=torch.uint8)
+            L.dtm_maxpool_fwd(_lib.ptr(x), _lib.ptr(out["y"]), _lib.ptr(out["arg"]), ctypes.byref(a), s)
+            L.dtm_maxpool_bwd(_lib.ptr(dy), _lib.ptr(out["arg"]), _lib.ptr(out["dx"]), ctypes.byref(a), s)
+            for cp in (0, 1):
+                out["avg_y%d" % cp], out["avg_dx%d" % cp] = torch.empty_like(dy), torch.empty_like(x)
+                L.dtm_avgpool_fwd(_lib.ptr(x), _lib.ptr(out["avg_y%d" % cp]), ctypes.byref(a), cp, s)
+                L.dtm_avgpool_bwd(_lib.ptr(dy), _lib.ptr(out["avg_dx%d" % cp]), ctypes.byref(a), cp, s)
+            torch.cuda.synchronize()
+        finally:
+            L.dtm_pool_set_k3s2(1)
+        return out
+
+    o20 = run(x20, dy20, False)
+    o16 = run(x20[..., :16].contiguous(), dy20[..., :16].contiguous(), k == 3)
+    for name in o20:
+        assert torch.equal(o16[name], o20[name][..., :16]), name
+    # fp32 torch (NCHW; TF SAME padding as explicit pads)
+    pads = (g.PW, g.PR, g.PH, g.PB)
+    gy = dy20.float().permute(0, 3, 1, 2)
+    xr = x20.float().permute(0, 3, 1, 2).contiguous().requires_grad_()
+    padded = tF.pad(xr, pads, value=-1e30)
+    yr = tF.max_pool2d(padded, k, st)
+    assert torch.equal(o20["y"].float().permute(0, 3, 1, 2), yr)
+    win = tF.unfold(padded.detach(), k, stride=st).view(2, 20, k * k, g.P, g.Q)  # taps in (r, s) order
+    assert torch.equal(o20["arg"].long().permute(0, 3, 1, 2), win.argmax(2))  # (the first maximum)
+    yr.backward(gy)
+    assert _rel(o20["dx"].float(), xr.grad.permute(0, 2, 3, 1)) < 2e-2  # (bf16 ties may route differently in torch)
+    for cp in (0, 1):
+        xr = x20.float().permute(0, 3, 1, 2).contiguous().requires_grad_()
+        yr = tF.avg_pool2d(tF.pad(xr, pads), k, st)
+        if not cp:  # TF SAME: divide by the in-bounds taps
+            yr = yr / tF.avg_pool2d(tF.pad(torch.ones_like(xr[:, :1]), pads), k, st)
+        assert _rel(o20["avg_y%d" % cp].float().permute(0, 3, 1, 2), yr) < 1e-2
+        yr.backward(gy)
+        assert _rel(o20["avg_dx%d" % cp].float(), xr.grad.permute(0, 2, 3, 1)) < 1e-2
+
+
 @pytest.mark.parametrize("case", [(4, 28, 28, 64, 256, True, True), (4, 28, 28, 64, 256, False, True),
                                   (3, 13, 13, 128, 512, True, False), (2, 9, 11, 128, 384, False, True),
                                   (5, 14, 14, 64, 128, True, True), (3, 14, 14, 256, 1024, False, True),

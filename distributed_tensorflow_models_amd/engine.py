@@ -104,15 +104,32 @@ def reserved_cus_default():
 RESERVED_CUS_DP = 0
 
 
+def _map_batches(fn, a, *more):
+    """fn over one batch (tensors) or over the micro-batches of a step (lists of tensors)."""
+    if isinstance(a, list):
+        return [fn(*t) for t in zip(a, *more)]
+    return fn(a, *more)
+
+
+def _stage(static, new):
+    if new.data_ptr() != static.data_ptr():
+        static.copy_(new, non_blocking=True)
+
+
 class TrainStep:
     def __init__(self, model, optimizer="momentum", lr=0.1, momentum=0.9, rho=0.9, epsilon=None, bucket_mb=32.0,
                  label_smoothing=0.0, aux_weight=0.4, ema_decay=None, lr_schedule=None, use_graph=False,
                  process_group=None, weight_decay=None, batch_weight=1.0, nan_guard=True, timer=None,
                  grad_comm_dtype=None, ema_buffers=True, bn_sync_every=1, wgrad_stream=None, bsp_check=None,
                  overlap=True, force_comm=False, graph_comm=False, lars_eeta=0.001, lars_epsilon=0.0,
-                 clip_global_norm=None, beta1=0.9, beta2=0.999):
+                 clip_global_norm=None, beta1=0.9, beta2=0.999, accum_steps=1):
         # epsilon None: the optimizer's own default (1e-10; Adam 1e-8); beta1 / beta2: Adam only
+        # accum_steps N: a call runs N micro-batches, sums their gradients (parallel/bsp.py begin_micro /
+        # accumulate) and applies ONE update: an effective batch of N times the micro-batch on the same memory
         self.model = model
+        self.accum_steps = int(accum_steps)
+        if self.accum_steps < 1:
+            raise ValueError("accum_steps must be at least 1, got %r" % (accum_steps,))
         if wgrad_stream is not None:
             # conv+BN weight gradients on the side stream (ops/_lib.py side_stream; process-wide): ResNet-50
             # -4.3 % step time, Inception-v3 +3.4 % eager (its per-conv stream forks cost more host time than
@@ -179,31 +196,69 @@ class TrainStep:
         if self.timer is not None:
             self.timer.mark(name)
 
+    def _micro_batches(self, images, labels):
+        """The step's ``accum_steps`` micro-batches as (list of images, list of labels): each argument is a list /
+        tuple of that length, or one tensor split into equal contiguous views along the leading dimension."""
+        n = self.accum_steps
+        out = []
+        for name, v in (("images", images), ("labels", labels)):
+            if isinstance(v, (list, tuple)):
+                if len(v) != n:
+                    raise ValueError("%s: %d micro-batches given, accum_steps is %d" % (name, len(v), n))
+                out.append(list(v))
+            else:
+                if v.shape[0] % n:
+                    raise ValueError("%s: leading dimension %d is not divisible by accum_steps %d"
+                                     % (name, v.shape[0], n))
+                b = v.shape[0] // n
+                out.append([v[i * b:(i + 1) * b] for i in range(n)])
+        return out[0], out[1]
+
     def _forward_backward(self, images, labels):
-        self.dp.zero_grad()
-        self._mark("start")
-        if images.is_cuda:
-            _fused.arena.begin_step(images.device)
-            _elementwise.advance_seed_offset(images.device)  # fresh dropout masks, replay included
-        try:
-            with roctx("forward"):
-                out = self.model(images, training=True)
-            with roctx("loss"):
-                loss = self.loss_fn(out, labels)
-            self._mark("fwd")
-            self.bufsync.issue()  # forward has finished every moving-statistics update
-            if self.on_backward is not None:
-                self.on_backward()
-            with roctx("backward"):  # bucket all-reduces are issued (own ranges) from the grad hooks
-                loss.backward()
+        """One batch (two tensors), or the micro-batches of one step (two lists of tensors): micro-batches
+        0 .. n-2 end in the accumulate launch, the last one folds and reduces."""
+        micro = list(zip(images, labels)) if isinstance(images, (list, tuple)) else [(images, labels)]
+        n = len(micro)
+        losses = []
+        for i, (images, labels) in enumerate(micro):
+            last = i == n - 1
+            self.dp.begin_micro(i, n)
+            if i == 0:
+                self._mark("start")
             if images.is_cuda:
-                _lib.side_join()  # weight gradients enqueued on the side stream (ops/_lib.py)
-            self._mark("bwd")
-        except BaseException:
-            self.bufsync.abort()  # the live BN statistics stay this replica's own (never a partial sum)
-            raise
-        finally:
-            _fused.arena.end_step()
+                _fused.arena.begin_step(images.device)
+                _elementwise.advance_seed_offset(images.device)  # fresh dropout masks, replay included
+            try:
+                with roctx("forward"):
+                    out = self.model(images, training=True)
+                with roctx("loss"):
+                    loss = self.loss_fn(out, labels)
+                if last:
+                    self._mark("fwd")
+                    self.bufsync.issue()  # forward has finished every moving-statistics update
+                else:
+                    self.bufsync.local_update()  # one more local update for the last micro-batch's sync to cover
+                if self.on_backward is not None:
+                    self.on_backward()
+                with roctx("backward"):  # bucket all-reduces are issued (own ranges) from the grad hooks
+                    loss.backward()
+                if images.is_cuda:
+                    _lib.side_join()  # weight gradients enqueued on the side stream (ops/_lib.py)
+                if last:
+                    self._mark("bwd")
+            except BaseException:
+                self.bufsync.abort()  # the live BN statistics stay this replica's own (never a partial sum)
+                raise
+            finally:
+                _fused.arena.end_step()
+            losses.append(loss.detach())
+            if not last:
+                self.dp.accumulate(i)
+        loss = losses[0]
+        if n > 1:  # fp32 mean of the micro-batch losses, summed in micro-batch order
+            for v in losses[1:]:
+                loss = loss + v
+            loss = loss / n
         with roctx("allreduce_wait"):
             self.dp.finish()
             self.bufsync.finish()
@@ -226,9 +281,21 @@ class TrainStep:
         return loss.detach(), skip
 
     def __call__(self, images, labels):
-        if self.use_graph and images.is_cuda:
+        """One optimizer step.  With ``accum_steps`` N > 1 each argument is a list / tuple of N micro-batches, or
+        one tensor whose leading dimension N divides (split into equal contiguous views): the gradients of the N
+        micro-batches are summed and applied once; the returned loss is the mean of their losses."""
+        if self.accum_steps > 1:
+            images, labels = self._micro_batches(images, labels)
+        if self.use_graph and (images[0] if self.accum_steps > 1 else images).is_cuda:
             return self._graph_step(images, labels)
         return self._eager_step(images, labels)
+
+    def nonfinite_micro(self):
+        """Per micro-batch of the last step, 1 where its gradients held an Inf or a NaN (this rank's own: the
+        flags are set before the all-reduce).  Reads the device: call on logged steps only."""
+        if self.accum_steps == 1 or self.dp.micro_flags is None:
+            return [0] * self.accum_steps
+        return [int(v) for v in self.dp.micro_flags.tolist()]
 
     def _eager_step(self, images, labels):
         rng = range_push("train_step")
@@ -260,8 +327,9 @@ class TrainStep:
             finally:
                 self.use_graph = True
         if self._graph is None:
-            self._static_x = images.clone()
-            self._static_y = labels.clone()
+            # (with accum_steps > 1: one static copy per micro-batch, all of them inside the one graph)
+            self._static_x = _map_batches(torch.Tensor.clone, images)
+            self._static_y = _map_batches(torch.Tensor.clone, labels)
             torch.cuda.synchronize()
             g = torch.cuda.CUDAGraph()
             timer, self.timer = self.timer, None  # no event records inside the capture
@@ -275,10 +343,8 @@ class TrainStep:
                 self.timer = timer
             self._graph, self._static_loss = g, loss
         else:
-            if images.data_ptr() != self._static_x.data_ptr():
-                self._static_x.copy_(images, non_blocking=True)
-            if labels.data_ptr() != self._static_y.data_ptr():
-                self._static_y.copy_(labels, non_blocking=True)
+            _map_batches(_stage, self._static_x, images)
+            _map_batches(_stage, self._static_y, labels)
         self.opt.set_dynamic(self.current_lr(), self.dp.grad_scale)
         self._graph.replay()
         self.opt.num_updates += 1

@@ -113,6 +113,7 @@ _SIGS = {
     "dtm_adam_state_bytes": (_I, []),
     "dtm_multi_tensor_adam": (_I, [_P, _P, _I, _D, _D, _D, _I, _P, _P, _P, _P, _P]),
     "dtm_check_finite": (None, [_P, _L, _P, _P]),
+    "dtm_grad_accum": (_I, [_P, _P, _L, _I, _P, _P]),
     "dtm_f32_to_bf16": (None, [_P, _P, _L, _P]),
     "dtm_scale": (None, [_P, _L, _F, _P]),
     "dtm_bn_apply_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _P]),

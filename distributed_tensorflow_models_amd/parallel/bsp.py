@@ -26,7 +26,11 @@ Design (MI355X-first):
   * ``comm_dtype=torch.bfloat16`` (opt-in) sends each bucket as bf16: the bucket is cast into a
     bf16 shadow right before its all-reduce and cast back after the wait - half the bytes on the
     xGMI links for communication-bound models (VGG-16: 537 MB of fp32 gradient per step), at the
-    cost of bf16 rounding of the per-rank and summed gradients.
+    cost of bf16 rounding of the per-rank and summed gradients (SURVEY.md M2);
+  * gradient accumulation (``begin_micro`` / ``accumulate``; TrainStep(accum_steps=N)): the micro-batches before the
+    last move their gradients into a second flat buffer of the same layout (one launch over the whole buffer, which
+    also clears the flat one) and issue no collective; the last one adds the accumulator to each bucket right before
+    that bucket's all-reduce (csrc/kernels/grad_accum.hip), so a step of N micro-batches costs the collectives of one.
 With world_size == 1 no collective is issued.
 """
 import os
@@ -35,6 +39,7 @@ import torch
 import torch.distributed as dist
 
 from ..ops import _lib
+from ..ops import accum as _accum
 from ..ops import nn as opsnn
 from ..utils.profiler import roctx
 
@@ -95,6 +100,11 @@ class BSPDataParallel:
         self._write_hook = opsnn.add_grad_write_hook(self._on_write) if self.check else None
         self.writes_checked = 0
         self.unreported = []
+        # gradient accumulation (begin_micro / accumulate): the accumulator, a second flat buffer of the same
+        # layout, and the per-micro-batch non-finite flags exist only once a step of several micro-batches ran
+        self.acc = None
+        self.micro_flags = None
+        self._micro = (0, 1)  # (index, count) of the micro-batch whose gradients the flat buffer is taking
 
     def _build_buckets(self):
         """Contiguous cap-sized buckets over the flat buffer, skipping the segments of windowed
@@ -178,12 +188,54 @@ class BSPDataParallel:
 
     # ------------------------------------------------------------------------------------------
     def zero_grad(self):
-        self.flat.zero_()
+        self.begin_micro(0, 1)
+
+    def begin_micro(self, i, n):
+        """Start micro-batch ``i`` of the ``n`` that make up this step (``zero_grad`` is ``begin_micro(0, 1)``).
+        The flat buffer is zeroed for the first one only: ``accumulate`` leaves it cleared for the others."""
+        if not 0 <= i < n:
+            raise ValueError("micro-batch %d of %d" % (i, n))
+        if n > 1 and (self.micro_flags is None or self.micro_flags.numel() != n):
+            if self.acc is None:
+                self.acc = torch.zeros_like(self.flat)
+            self.micro_flags = torch.zeros(n, dtype=torch.int32, device=self.flat.device)
+        self._micro = (i, n)
+        if i == 0:
+            self.flat.zero_()
+            if n > 1:
+                self.micro_flags.zero_()
         self._have = [0] * len(self.buckets)
         self._launched = [False] * len(self.buckets)
         self._works = []
         self._seen = set()
         self.unreported = []
+
+    def accumulate(self, i):
+        """After the backward of micro-batch ``i`` < n-1: move its gradients into the accumulator in one launch
+        over the whole buffer, which also clears the flat buffer for the next micro-batch.  No collective."""
+        idx, n = self._micro
+        if i != idx or i >= n - 1:
+            raise ValueError("accumulate(%d) during micro-batch %d of %d" % (i, idx, n))
+        if self.check:
+            self.unreported = [self._pname(p) for p in self.order if p not in self._seen]
+        if self.flat.is_cuda:
+            _lib.side_join()
+        with roctx("grad_accumulate"):
+            _accum.grad_accum(self.acc, self.flat, _accum.STORE if i == 0 else _accum.ADD,
+                              self.micro_flags[i:i + 1])
+        if self.check:
+            # nothing may write a gradient between this launch and the next begin_micro
+            self._seen = set(self.contrib)
+
+    def _fold(self, s, e):
+        """(last micro-batch) add the accumulated gradients of flat[s:e] to the ones the last backward wrote."""
+        n = self._micro[1]
+        if n > 1:
+            _accum.grad_accum(self.acc[s:e], self.flat[s:e], _accum.FOLD, self.micro_flags[n - 1:n])
+
+    def accum_bytes(self):
+        """Bytes the accumulation buffers hold (0 until a step of several micro-batches ran)."""
+        return 0 if self.acc is None else self.acc.numel() * self.acc.element_size()
 
     def _on_accumulated(self, p):
         # plain autograd path (CPU ops / torch fallbacks): move .grad into the flat buffer.  (autograd also
@@ -224,7 +276,8 @@ class BSPDataParallel:
         self._seen.add(p)
         for bi, n in lst:
             self._have[bi] += n
-            if self.overlap and self._have[bi] == self.need[bi]:
+            # (micro-batches before the last issue no collective: their gradients go to the accumulator)
+            if self.overlap and self._have[bi] == self.need[bi] and self._micro[0] == self._micro[1] - 1:
                 self._launch(bi)
 
     def _launch(self, bi):
@@ -247,12 +300,14 @@ class BSPDataParallel:
         with roctx("allreduce_bucket_%d" % bi):
             if bi in self.compact:
                 p, (r0, r1, s0, s1), buf, low = self.compact[bi]
+                self._fold(self.offsets[p], self.offsets[p] + p.numel())  # the whole segment: it is in no bucket
                 buf.copy_(p.main_grad[:, r0:r1, s0:s1, :])  # gather the live window
                 if low is not None:
                     low.copy_(buf)
                     buf = low
             else:
                 s, e = self.buckets[bi]
+                self._fold(s, e)  # after every write of the bucket on both streams, before the wire cast
                 buf = self.flat[s:e]
                 if self.comm is not None:
                     buf = self.comm[s:e]
@@ -270,6 +325,8 @@ class BSPDataParallel:
                 self._launch(bi)
         if self.flat.is_cuda:
             _lib.side_join()
+        if not self.comm_on:
+            self._fold(0, self.flat.numel())  # no collective, no per-bucket launch: one fold over the buffer
         for bi, w in self._works:
             w.wait()
             if bi in self.compact:
@@ -303,7 +360,8 @@ class BSPDataParallel:
 
     @property
     def grad_scale(self):
-        return 1.0 / self.world
+        # each micro-batch's loss is a mean over its rows: the applied gradient is the mean over all n * b * W rows
+        return 1.0 / (self.world * self._micro[1])
 
 
 def flatten_tensors(tensors):
@@ -388,6 +446,14 @@ class BufferSync:
 
     def begin(self):
         """(kept for API symmetry: the snapshot is the state after the last sync, see finish)"""
+
+    def local_update(self):
+        """A forward updated the statistics and no sync follows it (a micro-batch before the last of a step with
+        gradient accumulation): the next ``issue`` covers it in its k.  ``every`` keeps counting ``issue`` calls,
+        i.e. optimizer steps."""
+        if self.flat is None:
+            return
+        self._local += 1
 
     def issue(self):
         if self.flat is None:

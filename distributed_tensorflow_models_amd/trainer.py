@@ -112,6 +112,10 @@ ADAM_BSP_ONLY = ("--optimizer adam needs --sync_mode bsp (got %s): under asp / s
                  "which would need a shared count of applied updates per shard for the bias correction")
 
 
+ACCUM_BSP_ONLY = ("--accum_steps > 1 needs --sync_mode bsp (got %s): under asp / ssp every push is applied by the "
+                  "owner shards at once, so there is no step over which gradients could be summed")
+
+
 def define_common_flags(flags, preset):
     """Flags shared by every trainer (reference flag inventory) + MI355X extras."""
     p = PRESETS[preset]
@@ -156,6 +160,8 @@ def define_common_flags(flags, preset):
              "--initial_learning_rate to --end_learning_rate over --max_steps steps)"),
             ("end_learning_rate", Fl, 0.0001, "polynomial decay: the final learning rate"),
             ("lr_power", Fl, 1.0, "polynomial decay: the power"),
+            ("accum_steps", I, 1, "gradient accumulation: every step runs N micro-batches of --batch_size images and "
+             "applies one update from the sum of their gradients (BSP only; the learning rate is not rescaled)"),
             # MI355X-native extras
             ("sync_mode", S, "", "bsp | asp | ssp (default from the entry script)"),
             ("max_staleness", I, 5, "SSP staleness bound in local steps"),
@@ -260,6 +266,11 @@ def train(preset, flags, default_mode="bsp"):
         raise ValueError(LARGE_BATCH_BSP_ONLY % mode)
     if mode in ("asp", "ssp") and optimizer == "adam":
         raise ValueError(ADAM_BSP_ONLY % mode)
+    accum = int(FLAGS.accum_steps)
+    if accum < 1:
+        raise ValueError("--accum_steps must be at least 1, got %d" % accum)
+    if mode in ("asp", "ssp") and accum > 1:
+        raise ValueError(ACCUM_BSP_ONLY % mode)
     ps_hosts = [h for h in FLAGS.ps_hosts.split(",") if h]
     worker_hosts = [h for h in FLAGS.worker_hosts.split(",") if h]
     if FLAGS.job_name == "ps":
@@ -307,7 +318,8 @@ def train(preset, flags, default_mode="bsp"):
 
     # ---- schedule (C16, C19) ---------------------------------------------------------------------
     n_train = CIFAR_TRAIN if cfg["dataset"] in ("cifar10",) else IMAGENET_TRAIN
-    batches_per_epoch = n_train / float(B)
+    # (a step consumes accum * B images per worker: --batch_size stays the micro-batch, as in the reference)
+    batches_per_epoch = n_train / float(B * accum)
     decay_steps = batches_per_epoch * FLAGS.num_epochs_per_decay
     if cfg.get("decay_div_workers") and mode == "bsp":
         decay_steps /= max(world, 1)
@@ -357,7 +369,7 @@ def train(preset, flags, default_mode="bsp"):
                             timer=StepTimer() if (FLAGS.metrics_file and rank == 0 and not FLAGS.use_hipgraph)
                             else None, lars_eeta=FLAGS.lars_eeta, lars_epsilon=FLAGS.lars_epsilon,
                             clip_global_norm=FLAGS.clip_global_norm if FLAGS.clip_global_norm > 0 else None,
-                            beta1=FLAGS.adam_beta1, beta2=FLAGS.adam_beta2, **opt_kw)
+                            beta1=FLAGS.adam_beta1, beta2=FLAGS.adam_beta2, accum_steps=accum, **opt_kw)
         vars_ = model_variables(model, step_fn.opt, gstep, **ckpt_kw)
         vars_[-1].name = cfg.get("global_step_name", "global_step")
         if path:
@@ -445,7 +457,10 @@ def train(preset, flags, default_mode="bsp"):
             logging.error("fault injection: rank %d exits at step %d", rank, step)
             os._exit(17)
         tracer.step(step)
-        images, labels = data.next_batch()
+        if accum > 1:  # N micro-batches per step, handed over as lists (no concatenation copy)
+            images, labels = (list(v) for v in zip(*[data.next_batch() for _ in range(accum)]))
+        else:
+            images, labels = data.next_batch()
         if mode == "bsp":
             loss = step_fn(images, labels)
             gs = step_fn.global_step
@@ -461,7 +476,7 @@ def train(preset, flags, default_mode="bsp"):
              (t_summary is None or time.time() - t_summary >= FLAGS.save_summaries_secs)) or
             (FLAGS.save_summaries_steps > 0 and gs % FLAGS.save_summaries_steps == 0))
         if summ is not None and summ_now:
-            summ.launch(images)
+            summ.launch(images[-1] if accum > 1 else images)  # (the gradients are the whole step's)
         # the loss is read (a device sync) on log steps only; the NaN assertion of the reference
         # (imagenet_inception_bsp.py:191, every step) is checked there, and non-finite steps in
         # between are caught by the engine's device-side guard (update skipped, counted, reported)
@@ -479,7 +494,8 @@ def train(preset, flags, default_mode="bsp"):
             t_log, n_since = now, 0
         if cfg.get("nan_guard") and math.isnan(loss_v):  # imagenet_inception_bsp.py:191
             raise FloatingPointError("Model diverged with loss = NaN")
-        if mode == "bsp" and need_log and step_fn.poll_skipped():
+        skipped_now = mode == "bsp" and need_log and step_fn.poll_skipped()
+        if skipped_now:
             if cfg.get("nan_guard"):
                 # the reference asserts on a NaN loss every step; here the device-side guard skipped the update
                 # of a non-finite step and the check fires at the next log line (at most --log_every steps late)
@@ -489,7 +505,8 @@ def train(preset, flags, default_mode="bsp"):
                             step, step_fn.skipped)
         gstep.fill_(gs)
         if log_now:
-            print(format_step(cfg["log_style"], step, gs, loss_v, B / max(dt, 1e-9), dt), flush=True)
+            ips = accum * B / max(dt, 1e-9)  # images of the whole step: accum micro-batches of B
+            print(format_step(cfg["log_style"], step, gs, loss_v, ips, dt), flush=True)
             if tbw is not None and loss_v == loss_v:
                 loss_avg = loss_v if loss_avg is None else 0.9 * loss_avg + 0.1 * loss_v
                 if summ_now:
@@ -497,7 +514,7 @@ def train(preset, flags, default_mode="bsp"):
                     tbw.add_scalar("learning_rate", float(sched(gs)), gs)
                     tbw.add_scalar("total_loss (raw)", loss_v, gs)
                     tbw.add_scalar("total_loss", loss_avg, gs)
-                    tbw.add_scalar("images_per_sec", world * B / max(dt, 1e-9), gs)
+                    tbw.add_scalar("images_per_sec", world * ips, gs)
             if summ is not None and summ_now:
                 summ.write(tbw, gs)
             extra = step_fn.timer.sections() if (mode == "bsp" and step_fn.timer is not None) else {}
@@ -524,9 +541,12 @@ def train(preset, flags, default_mode="bsp"):
                     extra["bucket_allreduce_ms"] = bms
             if device.type == "cuda" and metrics.f is not None:
                 extra["max_mem_gb"] = torch.cuda.max_memory_allocated(device) / 2 ** 30
-            metrics.write(step=step, global_step=gs, loss=loss_v, lr=sched(gs), images_per_sec=B / max(dt, 1e-9),
-                          node_images_per_sec=world * B / max(dt, 1e-9), step_ms=dt * 1e3, world=world, mode=mode,
-                          **extra)
+            if skipped_now and metrics.f is not None:
+                # which micro-batches of THIS step were non-finite on this rank (the skip may be an earlier step's)
+                extra["nonfinite_micro_batches"] = step_fn.nonfinite_micro()
+            metrics.write(step=step, global_step=gs, loss=loss_v, lr=sched(gs), images_per_sec=ips,
+                          node_images_per_sec=world * ips, step_ms=dt * 1e3, world=world, mode=mode,
+                          accum_steps=accum, **extra)
         # every worker runs the probe, as every reference worker does (resnet/cifar10_resnet_bsp.py:146-148)
         if FLAGS.train_accuracy_every and step % FLAGS.train_accuracy_every == 0:
             if probe is None:

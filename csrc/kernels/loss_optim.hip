@@ -27,11 +27,16 @@ template <>
 __device__ __forceinline__ float ldf<bf16_t>(const bf16_t* p, long i) { return bf2f(p[i]); }
 
 // one block per row; labels int32; out_loss[row]; dlogits fp32 or bf16 (same type as logits)
-template <typename T>
-__global__ __launch_bounds__(256) void softmax_xent_kernel(const T* __restrict__ logits, const int* __restrict__ labels,
-                                                           float* __restrict__ loss, T* __restrict__ dlogits, int K,
-                                                           float smoothing, float gscale, const float* row_weight,
-                                                           int ldx) {
+// MIX (dtm_softmax_xent_mix): the row has two labels, la = labels[row] and lb = labels[partner], with weights wl and
+// 1 - wl from the row's mixing record (mix.hip: [partner, bits(w_pix), bits(w_lab), ...], 8 int32), and the target
+//   t_k = off + (on - off) * (wl * [k == la] + (1 - wl) * [k == lb]).
+// A target weight of exactly 1 or 0 takes the plain kernel's own expressions, so a row with wl == 1 gets the bits
+// softmax_xent_kernel gives it with labels[row]; an out-of-range label contributes nothing, on either side.
+template <typename T, bool MIX>
+__device__ __forceinline__ void softmax_xent_body(const T* __restrict__ logits, const int* __restrict__ labels,
+                                                  float* __restrict__ loss, T* __restrict__ dlogits, int K,
+                                                  float smoothing, float gscale, const float* row_weight, int ldx,
+                                                  const int* __restrict__ plan) {
   __shared__ float red[8];
   const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const T* x = logits + (long)row * ldx;  // (ldx: row pitch - an FC's padded output read in place)
@@ -57,10 +62,20 @@ __global__ __launch_bounds__(256) void softmax_xent_kernel(const T* __restrict__
   sx = red[4] + red[5] + red[6] + red[7];
   const float lse = m + __logf(s);
   const int lab = labels[row];
+  int lab2 = -1;
+  float wl = 1.f;
+  if constexpr (MIX) {
+    lab2 = labels[plan[(long)row * 8]];
+    wl = __int_as_float(plan[(long)row * 8 + 2]);
+  }
   const float on = 1.f - smoothing + smoothing / K, off = smoothing / K;
   const float w = row_weight ? row_weight[row] : 1.f;
   if (tid == 0) {
     float xl = (lab >= 0 && lab < K) ? ldf(x, lab) : 0.f;
+    if constexpr (MIX) {
+      const float xl2 = (lab2 >= 0 && lab2 < K) ? ldf(x, lab2) : 0.f;
+      if (wl != 1.f) xl = wl * xl + (1.f - wl) * xl2;
+    }
     // -sum_k t_k log p_k = lse - sum_k t_k x_k
     loss[row] = w * (lse - (off * sx + (on - off) * xl));
   }
@@ -69,11 +84,32 @@ __global__ __launch_bounds__(256) void softmax_xent_kernel(const T* __restrict__
     for (int k = tid; k < K; k += 256) {
       float p = __expf(ldf(x, k) - lse);
       float t = (k == lab) ? on : off;
+      if constexpr (MIX) {
+        const float m = (k == lab ? wl : 0.f) + (k == lab2 ? 1.f - wl : 0.f);  // the target's share of "on"
+        t = m == 1.f ? on : m == 0.f ? off : off + (on - off) * m;
+      }
       float gv = (p - t) * gscale * w;
       if constexpr (sizeof(T) == 4) d[k] = gv;
       else d[k] = f2bf(gv);
     }
   }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void softmax_xent_kernel(const T* __restrict__ logits, const int* __restrict__ labels,
+                                                           float* __restrict__ loss, T* __restrict__ dlogits, int K,
+                                                           float smoothing, float gscale, const float* row_weight,
+                                                           int ldx) {
+  softmax_xent_body<T, false>(logits, labels, loss, dlogits, K, smoothing, gscale, row_weight, ldx, nullptr);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void softmax_xent_mix_kernel(const T* __restrict__ logits,
+                                                               const int* __restrict__ labels,
+                                                               const int* __restrict__ plan, float* __restrict__ loss,
+                                                               T* __restrict__ dlogits, int K, float smoothing,
+                                                               float gscale, int ldx) {
+  softmax_xent_body<T, true>(logits, labels, loss, dlogits, K, smoothing, gscale, nullptr, ldx, plan);
 }
 
 struct OptTensor {
@@ -473,6 +509,21 @@ DTM_API void dtm_softmax_xent(const void* logits, int logits_bf16, const int* la
   else
     hipLaunchKernelGGL(softmax_xent_kernel<float>, dim3(B), dim3(256), 0, (hipStream_t)stream, (const float*)logits,
                        labels, loss, (float*)dlogits, K, smoothing, gscale, row_weight, ldx);
+}
+
+// The two-label loss of a mixed batch (softmax_xent_body<T, true>): plan is the batch's device record of mix.hip, B
+// rows of 8 int32, trusted (0 <= partner < B).  Returns -1 for a bad argument.
+DTM_API int dtm_softmax_xent_mix(const void* logits, int logits_bf16, const int* labels, const int* plan, float* loss,
+                                 void* dlogits, int B, int K, float smoothing, float gscale, int ldx, void* stream) {
+  if (!logits || !labels || !plan || !loss || B < 1 || K < 1) return -1;
+  if (ldx < K) ldx = K;
+  if (logits_bf16)
+    hipLaunchKernelGGL(softmax_xent_mix_kernel<bf16_t>, dim3(B), dim3(256), 0, (hipStream_t)stream,
+                       (const bf16_t*)logits, labels, plan, loss, (bf16_t*)dlogits, K, smoothing, gscale, ldx);
+  else
+    hipLaunchKernelGGL(softmax_xent_mix_kernel<float>, dim3(B), dim3(256), 0, (hipStream_t)stream,
+                       (const float*)logits, labels, plan, loss, (float*)dlogits, K, smoothing, gscale, ldx);
+  return 0;
 }
 
 DTM_API int dtm_loss_combine(const float* loss, int heads, int B, const float* w, float* out, void* stream) {

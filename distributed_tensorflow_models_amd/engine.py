@@ -12,6 +12,7 @@ import torch
 from .ops import _lib
 from .ops import elementwise as _elementwise
 from .ops import fused as _fused
+from .ops import mix as _mix
 from .ops import nn as F
 from .ops.optim import FusedOptimizer
 from .parallel.bsp import BSPDataParallel, BufferSync
@@ -122,11 +123,20 @@ class TrainStep:
                  process_group=None, weight_decay=None, batch_weight=1.0, nan_guard=True, timer=None,
                  grad_comm_dtype=None, ema_buffers=True, bn_sync_every=1, wgrad_stream=None, bsp_check=None,
                  overlap=True, force_comm=False, graph_comm=False, lars_eeta=0.001, lars_epsilon=0.0,
-                 clip_global_norm=None, beta1=0.9, beta2=0.999, accum_steps=1):
+                 clip_global_norm=None, beta1=0.9, beta2=0.999, accum_steps=1, mix=None, rank=None):
         # epsilon None: the optimizer's own default (1e-10; Adam 1e-8); beta1 / beta2: Adam only
         # accum_steps N: a call runs N micro-batches, sums their gradients (parallel/bsp.py begin_micro /
         # accumulate) and applies ONE update: an effective batch of N times the micro-batch on the same memory
+        # mix: an ops.mix.MixConfig - every micro-batch is mixed with a permutation of itself (mixup / CutMix) into
+        # a buffer this step owns and the loss takes both labels; the plan of micro-batch i of step s is
+        # sample_plan(mix, rank, s, i, ...).  None: nothing is constructed, today's launches and bits.
+        # rank: the rank the plans are drawn for (default: the process group's)
         self.model = model
+        if mix is not None and not isinstance(mix, _mix.MixConfig):
+            raise ValueError("mix must be an ops.mix.MixConfig or None, got %r" % (mix,))
+        self.mix = mix
+        self._mix_bufs = {}       # (shape, dtype, device) -> the mixed batch
+        self._mix_lambda = None   # mean w_lab over the last step's plans (host)
         self.accum_steps = int(accum_steps)
         if self.accum_steps < 1:
             raise ValueError("accum_steps must be at least 1, got %r" % (accum_steps,))
@@ -160,6 +170,10 @@ class TrainStep:
                                   if (ema_decay is not None and ema_buffers) else (),
                                   lars_eeta=lars_eeta, lars_epsilon=lars_epsilon, clip_global_norm=clip_global_norm,
                                   beta1=beta1, beta2=beta2)
+        if rank is None:
+            import torch.distributed as dist
+            rank = dist.get_rank(process_group) if dist.is_available() and dist.is_initialized() else 0
+        self.rank = int(rank)
         self.lr = lr
         self.lr_schedule = lr_schedule
         self.smoothing = label_smoothing
@@ -179,13 +193,42 @@ class TrainStep:
         if self.dp.world > 1 and params and params[0].is_cuda:
             _lib.set_reserved_cus(reserved_cus_default())
 
-    def loss_fn(self, out, labels):
+    def loss_fn(self, out, labels, plan=None):
         aux = None
         if isinstance(out, tuple):
             out, aux = out
         bw = self.batch_weight
         heads = [(out, bw)] + ([(aux, self.aux_weight * bw)] if aux is not None and self.aux_weight else [])
-        return F.mean_xent_loss(heads, labels, self.smoothing)
+        if plan is None:
+            return F.mean_xent_loss(heads, labels, self.smoothing)
+        return F.mean_xent_loss(heads, labels, self.smoothing, mix=plan)
+
+    # ---- mixup / CutMix (ops/mix.py) ---------------------------------------------------------
+    def _draw_plans(self, images):
+        """The host plans of this step's micro-batches (a pure function of the config, the rank, the step count
+        and the micro-batch index) and their mean label weight."""
+        micro = images if isinstance(images, (list, tuple)) else [images]
+        for x in micro:
+            if x.dim() != 4:
+                raise ValueError("mix needs [B, H, W, C] image batches, got shape %r" % (tuple(x.shape),))
+        plans = [_mix.sample_plan(self.mix, self.rank, self.global_step, i, x.shape[0], x.shape[1], x.shape[2])
+                 for i, x in enumerate(micro)]
+        self._mix_lambda = float(sum(float(p.w_lab.sum(dtype="float64")) for p in plans) / sum(p.B for p in plans))
+        return plans
+
+    def _mixed(self, images, plan):
+        """``images`` mixed under ``plan`` into the step's own buffer of that shape (never the caller's tensor:
+        the synthetic pipelines hand the same batch in for ever)."""
+        key = (tuple(images.shape), images.dtype, images.device)
+        buf = self._mix_bufs.get(key)
+        if buf is None:
+            buf = self._mix_bufs[key] = torch.empty_like(images, memory_format=torch.contiguous_format)
+        return _mix.mix_images(images.contiguous(), plan, out=buf)
+
+    def last_mix_lambda(self):
+        """Mean w_lab (the weight of a row's own label) over the last step's plans; a host value, nothing is read
+        from the device.  None without mixing or before the first step."""
+        return self._mix_lambda
 
     def current_lr(self):
         if self.lr_schedule is not None:
@@ -214,9 +257,14 @@ class TrainStep:
                 out.append([v[i * b:(i + 1) * b] for i in range(n)])
         return out[0], out[1]
 
-    def _forward_backward(self, images, labels):
+    def _forward_backward(self, images, labels, plans=None):
         """One batch (two tensors), or the micro-batches of one step (two lists of tensors): micro-batches
-        0 .. n-2 end in the accumulate launch, the last one folds and reduces."""
+        0 .. n-2 end in the accumulate launch, the last one folds and reduces.  ``plans`` (mixing only): one
+        MixPlan per micro-batch with its record on the device (the captured step's static ones); None: drawn
+        here and copied to the device."""
+        if self.mix is not None and plans is None:
+            plans = [p.to(x.device) for p, x in zip(self._draw_plans(images),
+                                                    images if isinstance(images, (list, tuple)) else [images])]
         micro = list(zip(images, labels)) if isinstance(images, (list, tuple)) else [(images, labels)]
         n = len(micro)
         losses = []
@@ -229,10 +277,13 @@ class TrainStep:
                 _fused.arena.begin_step(images.device)
                 _elementwise.advance_seed_offset(images.device)  # fresh dropout masks, replay included
             try:
+                if plans is not None:
+                    with roctx("mix"):
+                        images = self._mixed(images, plans[i])
                 with roctx("forward"):
                     out = self.model(images, training=True)
                 with roctx("loss"):
-                    loss = self.loss_fn(out, labels)
+                    loss = self.loss_fn(out, labels) if plans is None else self.loss_fn(out, labels, plans[i])
                 if last:
                     self._mark("fwd")
                     self.bufsync.issue()  # forward has finished every moving-statistics update
@@ -330,12 +381,18 @@ class TrainStep:
             # (with accum_steps > 1: one static copy per micro-batch, all of them inside the one graph)
             self._static_x = _map_batches(torch.Tensor.clone, images)
             self._static_y = _map_batches(torch.Tensor.clone, labels)
+            # mixing: one static record per micro-batch; the captured mix kernel and loss read it, and the kind of
+            # mixing is data in it (no host decision lives inside the capture)
+            self._static_plans = None
+            if self.mix is not None:
+                self._static_plans = [p.to(x.device) for p, x in zip(
+                    self._draw_plans(images), images if isinstance(images, list) else [images])]
             torch.cuda.synchronize()
             g = torch.cuda.CUDAGraph()
             timer, self.timer = self.timer, None  # no event records inside the capture
             try:
                 with torch.cuda.graph(g):
-                    loss, skip = self._forward_backward(self._static_x, self._static_y)
+                    loss, skip = self._forward_backward(self._static_x, self._static_y, self._static_plans)
                     self.opt.launch(skip)
                     from .ops.nn import refresh_flipped
                     refresh_flipped()
@@ -345,6 +402,11 @@ class TrainStep:
         else:
             _map_batches(_stage, self._static_x, images)
             _map_batches(_stage, self._static_y, labels)
+            if self.mix is not None:
+                # a fresh pinned tensor per plan: torch's host allocator recycles it only after the copy's stream
+                # event, so the next step's records never overwrite one whose copy has not run
+                for static, plan in zip(self._static_plans, self._draw_plans(images)):
+                    static.dev.copy_(plan.host_tensor(pin=True), non_blocking=True)
         self.opt.set_dynamic(self.current_lr(), self.dp.grad_scale)
         self._graph.replay()
         self.opt.num_updates += 1

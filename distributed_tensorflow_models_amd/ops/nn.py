@@ -908,12 +908,64 @@ class _MeanXentFn(torch.autograd.Function):
         return (None, None, None) + tuple(_scaled_rows_grad(dl, gl) for dl in ctx.saved_tensors)
 
 
-def mean_xent_loss(heads, labels, smoothing=0.0):
+class _MeanXentMixFn(torch.autograd.Function):
+    """_MeanXentFn for a mixed batch (ops/mix.py): every head's rows take two labels, labels[r] and
+    labels[partner[r]], weighted w_lab and 1 - w_lab from the plan's device record (dtm_softmax_xent_mix gathers
+    the partner's label itself).  The combine launch and the backward are _MeanXentFn's."""
+
+    @staticmethod
+    def forward(ctx, labels, plan_dev, smoothing, weights, *logits):
+        L = _lib.lib()
+        B = labels.shape[0]
+        lab = labels.to(torch.int32).contiguous()
+        losses = torch.empty((len(logits), B), device=lab.device, dtype=torch.float32)
+        dls = []
+        for i, (lg, w) in enumerate(zip(logits, weights)):
+            lg, ld = _rows(lg)
+            dl = torch.empty(lg.shape, device=lg.device, dtype=lg.dtype)
+            _check(L.dtm_softmax_xent_mix(_lib.ptr(lg), int(lg.dtype == torch.bfloat16), _lib.ptr(lab),
+                                          _lib.ptr(plan_dev), _lib.ptr(losses[i]), _lib.ptr(dl), B, lg.shape[1],
+                                          float(smoothing), float(w) / B, ld, _lib.stream_ptr()), "softmax_xent_mix")
+            dls.append(dl)
+        out = torch.empty((), device=lab.device, dtype=torch.float32)
+        ws = (ctypes.c_float * len(weights))(*[float(w) / B for w in weights])
+        _check(L.dtm_loss_combine(_lib.ptr(losses), len(logits), B, ctypes.cast(ws, ctypes.c_void_p), _lib.ptr(out),
+                                  _lib.stream_ptr()), "loss_combine")
+        ctx.save_for_backward(*dls)
+        return out
+
+    @staticmethod
+    def backward(ctx, gl):
+        gl = gl.float().reshape(1).contiguous()
+        return (None, None, None, None) + tuple(_scaled_rows_grad(dl, gl) for dl in ctx.saved_tensors)
+
+
+def mean_xent_loss(heads, labels, smoothing=0.0, mix=None):
     """sum over (logits, weight) heads of weight * mean softmax cross-entropy (the training loss with Inception's
-    weighted aux head); one fused op on the GPU, the plain composition elsewhere."""
+    weighted aux head); one fused op on the GPU, the plain composition elsewhere.  ``mix``: the batch's MixPlan
+    (ops/mix.py) - row r's loss is w_lab[r] * xent(labels[r]) + (1 - w_lab[r]) * xent(labels[partner[r]]), i.e. the
+    cross-entropy against the mix of the two labels' (smoothed) targets."""
     heads = [(lg, float(w)) for lg, w in heads]
     ok = all(lg.is_cuda and lg.dim() == 2 and lg.dtype in (torch.float32, torch.bfloat16) for lg, _ in heads)
-    if ok and labels.is_cuda and 1 <= len(heads) <= 4 and labels.shape[0] <= 65535:
+    ok = ok and labels.is_cuda and 1 <= len(heads) <= 4 and labels.shape[0] <= 65535
+    if mix is not None:
+        if mix.B != labels.shape[0]:
+            raise ValueError("mixing plan of %d rows used on %d labels" % (mix.B, labels.shape[0]))
+        mix.validate()  # the host copy, before anything is launched: the kernel trusts the device copy
+        if ok and mix.dev is not None and mix.dev.device == labels.device:
+            return _MeanXentMixFn.apply(labels, mix.dev, float(smoothing), [w for _, w in heads],
+                                        *[lg for lg, _ in heads])
+        wl = torch.from_numpy(mix.w_lab.copy()).to(labels.device)
+        partner_labels = labels[torch.from_numpy(mix.partner.astype("int64")).to(labels.device)]
+        loss = None
+        for lg, w in heads:
+            la = softmax_cross_entropy(lg, labels, smoothing)
+            lb = softmax_cross_entropy(lg, partner_labels, smoothing)
+            term = (wl * la + (1.0 - wl) * lb).mean()
+            term = term if w == 1.0 else w * term
+            loss = term if loss is None else loss + term
+        return loss
+    if ok:
         return _MeanXentFn.apply(labels, float(smoothing), [w for _, w in heads], *[lg for lg, _ in heads])
     loss = None
     for lg, w in heads:

@@ -116,6 +116,10 @@ ACCUM_BSP_ONLY = ("--accum_steps > 1 needs --sync_mode bsp (got %s): under asp /
                   "owner shards at once, so there is no step over which gradients could be summed")
 
 
+MIX_BSP_ONLY = ("--mixup_alpha / --cutmix_alpha need --sync_mode bsp (got %s): the mixing plans are drawn per global "
+                "step, which under asp / ssp is no property of a worker's own batch sequence")
+
+
 def define_common_flags(flags, preset):
     """Flags shared by every trainer (reference flag inventory) + MI355X extras."""
     p = PRESETS[preset]
@@ -162,6 +166,12 @@ def define_common_flags(flags, preset):
             ("lr_power", Fl, 1.0, "polynomial decay: the power"),
             ("accum_steps", I, 1, "gradient accumulation: every step runs N micro-batches of --batch_size images and "
              "applies one update from the sum of their gradients (BSP only; the learning rate is not rescaled)"),
+            # mixup / CutMix (ops/mix.py; BSP only; the sampler's seed is --seed)
+            ("mixup_alpha", Fl, 0.0, "mixup: Beta(alpha, alpha) parameter of the blend weight (0 = off)"),
+            ("cutmix_alpha", Fl, 0.0, "CutMix: Beta(alpha, alpha) parameter of the kept area (0 = off)"),
+            ("mix_prob", Fl, 1.0, "probability that a batch (a row with --mix_per_row) is mixed at all"),
+            ("mix_switch_prob", Fl, 0.5, "with both alphas above 0: the probability of CutMix over mixup"),
+            ("mix_per_row", B, False, "draw kind, weight and box per row instead of per batch"),
             # MI355X-native extras
             ("sync_mode", S, "", "bsp | asp | ssp (default from the entry script)"),
             ("max_staleness", I, 5, "SSP staleness bound in local steps"),
@@ -271,6 +281,13 @@ def train(preset, flags, default_mode="bsp"):
         raise ValueError("--accum_steps must be at least 1, got %d" % accum)
     if mode in ("asp", "ssp") and accum > 1:
         raise ValueError(ACCUM_BSP_ONLY % mode)
+    mix_cfg = None
+    if FLAGS.mixup_alpha != 0 or FLAGS.cutmix_alpha != 0:
+        if mode in ("asp", "ssp"):
+            raise ValueError(MIX_BSP_ONLY % mode)
+        from .ops.mix import MixConfig
+        mix_cfg = MixConfig(FLAGS.mixup_alpha, FLAGS.cutmix_alpha, FLAGS.mix_prob, FLAGS.mix_switch_prob,
+                            FLAGS.mix_per_row, seed=FLAGS.seed)
     ps_hosts = [h for h in FLAGS.ps_hosts.split(",") if h]
     worker_hosts = [h for h in FLAGS.worker_hosts.split(",") if h]
     if FLAGS.job_name == "ps":
@@ -369,7 +386,8 @@ def train(preset, flags, default_mode="bsp"):
                             timer=StepTimer() if (FLAGS.metrics_file and rank == 0 and not FLAGS.use_hipgraph)
                             else None, lars_eeta=FLAGS.lars_eeta, lars_epsilon=FLAGS.lars_epsilon,
                             clip_global_norm=FLAGS.clip_global_norm if FLAGS.clip_global_norm > 0 else None,
-                            beta1=FLAGS.adam_beta1, beta2=FLAGS.adam_beta2, accum_steps=accum, **opt_kw)
+                            beta1=FLAGS.adam_beta1, beta2=FLAGS.adam_beta2, accum_steps=accum, mix=mix_cfg, rank=rank,
+                            **opt_kw)
         vars_ = model_variables(model, step_fn.opt, gstep, **ckpt_kw)
         vars_[-1].name = cfg.get("global_step_name", "global_step")
         if path:
@@ -530,6 +548,8 @@ def train(preset, flags, default_mode="bsp"):
                 extra.update(ns)
             if mode == "bsp" and optimizer == "adam" and metrics.f is not None:
                 extra["adam_step"] = step_fn.opt.adam_step()  # applied updates: lags global_step after a NaN skip
+            if mix_cfg is not None and metrics.f is not None:
+                extra["mix_lambda"] = step_fn.last_mix_lambda()  # mean own-label weight of this step (a host value)
             if metrics.f is not None and getattr(mkw.get("quantize"), "fused", False):
                 # device reads, after the logged step's synchronisation above
                 from .ops import fakequant

@@ -32,35 +32,83 @@ __device__ __forceinline__ float ldf<bf16_t>(const bf16_t* p, long i) { return b
 //   t_k = off + (on - off) * (wl * [k == la] + (1 - wl) * [k == lb]).
 // A target weight of exactly 1 or 0 takes the plain kernel's own expressions, so a row with wl == 1 gets the bits
 // softmax_xent_kernel gives it with labels[row]; an out-of-range label contributes nothing, on either side.
-template <typename T, bool MIX>
+// DISTILL (dtm_softmax_xent_distill): a soft-target term against the teacher's row z at temperature T (Hinton et al.
+// 2015), with pT = softmax(x / T), q = softmax(z / T) and hard the loss above:
+//   kl   = sum_k q_k (log q_k - log pT_k)
+//   loss = (1 - a) * hard + a * T^2 * kl,   dlogits_k = gscale * ((1 - a) * (p_k - t_k) + a * T * (pT_k - q_k)).
+// The teacher's terms ride in the same three passes (its maximum with the row's; its sums with the row's).  With
+//   A = sum_k e^((z_k - mz) / T) * ((z_k - mz) - (x_k - m)),  Zq = sum_k e^((z_k - mz) / T),
+//   Zp = sum_k e^((x_k - m) / T)
+// kl = (A / Zq) / T - log Zq + log Zp: the row maxima cancel in the sum instead of in the result.  Every hard-loss
+// expression is the one above and the two terms are combined as (1 - a) * u + a * v, so a == 0 with a finite teacher
+// row gives the bits of the plain (MIX: the mixed) kernel.  A non-finite teacher logit is not special-cased: the
+// row's loss and gradient are non-finite and the step's NaN guard skips the update.
+template <typename T, bool MIX, bool DISTILL = false>
 __device__ __forceinline__ void softmax_xent_body(const T* __restrict__ logits, const int* __restrict__ labels,
                                                   float* __restrict__ loss, T* __restrict__ dlogits, int K,
                                                   float smoothing, float gscale, const float* row_weight, int ldx,
-                                                  const int* __restrict__ plan) {
-  __shared__ float red[8];
+                                                  const int* __restrict__ plan, const T* __restrict__ teacher = nullptr,
+                                                  int ldt = 0, float* __restrict__ kl_out = nullptr, float alpha = 0.f,
+                                                  float temperature = 1.f) {
+  __shared__ float red[DISTILL ? 20 : 8];
   const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const T* x = logits + (long)row * ldx;  // (ldx: row pitch - an FC's padded output read in place)
-  float m = -INFINITY;
-  for (int k = tid; k < K; k += 256) m = fmaxf(m, ldf(x, k));
+  const T* z = DISTILL ? teacher + (long)row * ldt : nullptr;
+  const float rT = 1.f / temperature;
+  float m = -INFINITY, mz = -INFINITY;
+  for (int k = tid; k < K; k += 256) {
+    m = fmaxf(m, ldf(x, k));
+    if constexpr (DISTILL) mz = fmaxf(mz, ldf(z, k));
+  }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
   if (lane == 0) red[wv] = m;
+  if constexpr (DISTILL) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mz = fmaxf(mz, __shfl_xor(mz, o, 64));
+    if (lane == 0) red[4 + wv] = mz;
+  }
   __syncthreads();
   m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  if constexpr (DISTILL) mz = fmaxf(fmaxf(red[4], red[5]), fmaxf(red[6], red[7]));
   __syncthreads();
   float s = 0.f, sx = 0.f;
+  float zp = 0.f, zq = 0.f, za = 0.f;  // DISTILL: Zp, Zq, A
   for (int k = tid; k < K; k += 256) {
     float v = ldf(x, k);
     s += __expf(v - m);
     sx += v;
+    if constexpr (DISTILL) {
+      const float dz = ldf(z, k) - mz, dx = v - m;
+      const float eq = __expf(dz * rT);
+      zp += __expf(dx * rT);
+      zq += eq;
+      za += eq * (dz - dx);
+    }
   }
   s = warp_sum(s);
   sx = warp_sum(sx);
   if (lane == 0) { red[wv] = s; red[4 + wv] = sx; }
+  if constexpr (DISTILL) {
+    zp = warp_sum(zp);
+    zq = warp_sum(zq);
+    za = warp_sum(za);
+    if (lane == 0) { red[8 + wv] = zp; red[12 + wv] = zq; red[16 + wv] = za; }
+  }
   __syncthreads();
   s = red[0] + red[1] + red[2] + red[3];
   sx = red[4] + red[5] + red[6] + red[7];
   const float lse = m + __logf(s);
+  float lzp = 0.f, lzq = 0.f, kl = 0.f;
+  if constexpr (DISTILL) {  // the four waves in a fixed order, as above
+    zp = (red[8] + red[9]) + (red[10] + red[11]);
+    zq = (red[12] + red[13]) + (red[14] + red[15]);
+    za = (red[16] + red[17]) + (red[18] + red[19]);
+    lzp = logf(zp);
+    lzq = logf(zq);
+    kl = (za / zq) * rT - lzq + lzp;
+  }
+  const float oma = 1.f - alpha;
   const int lab = labels[row];
   int lab2 = -1;
   float wl = 1.f;
@@ -77,18 +125,30 @@ __device__ __forceinline__ void softmax_xent_body(const T* __restrict__ logits, 
       if (wl != 1.f) xl = wl * xl + (1.f - wl) * xl2;
     }
     // -sum_k t_k log p_k = lse - sum_k t_k x_k
-    loss[row] = w * (lse - (off * sx + (on - off) * xl));
+    const float hard = w * (lse - (off * sx + (on - off) * xl));
+    if constexpr (DISTILL) {
+      loss[row] = oma * hard + (alpha * temperature * temperature) * kl;
+      if (kl_out) kl_out[row] = kl;
+    } else {
+      loss[row] = hard;
+    }
   }
   if (dlogits) {
     T* d = dlogits + (long)row * K;
     for (int k = tid; k < K; k += 256) {
-      float p = __expf(ldf(x, k) - lse);
+      const float v = ldf(x, k);
+      float p = __expf(v - lse);
       float t = (k == lab) ? on : off;
       if constexpr (MIX) {
         const float m = (k == lab ? wl : 0.f) + (k == lab2 ? 1.f - wl : 0.f);  // the target's share of "on"
         t = m == 1.f ? on : m == 0.f ? off : off + (on - off) * m;
       }
-      float gv = (p - t) * gscale * w;
+      float g = p - t;
+      if constexpr (DISTILL) {
+        const float pT = __expf((v - m) * rT - lzp), q = __expf((ldf(z, k) - mz) * rT - lzq);
+        g = oma * g + (alpha * temperature) * (pT - q);
+      }
+      float gv = g * gscale * w;
       if constexpr (sizeof(T) == 4) d[k] = gv;
       else d[k] = f2bf(gv);
     }
@@ -110,6 +170,15 @@ __global__ __launch_bounds__(256) void softmax_xent_mix_kernel(const T* __restri
                                                                T* __restrict__ dlogits, int K, float smoothing,
                                                                float gscale, int ldx) {
   softmax_xent_body<T, true>(logits, labels, loss, dlogits, K, smoothing, gscale, nullptr, ldx, plan);
+}
+
+template <typename T, bool MIX>
+__global__ __launch_bounds__(256) void softmax_xent_distill_kernel(
+    const T* __restrict__ logits, const T* __restrict__ teacher, int ldt, const int* __restrict__ labels,
+    const int* __restrict__ plan, float* __restrict__ loss, float* __restrict__ kl, T* __restrict__ dlogits, int K,
+    float smoothing, float alpha, float temperature, float gscale, int ldx) {
+  softmax_xent_body<T, MIX, true>(logits, labels, loss, dlogits, K, smoothing, gscale, nullptr, ldx, plan, teacher, ldt,
+                                  kl, alpha, temperature);
 }
 
 struct OptTensor {
@@ -523,6 +592,41 @@ DTM_API int dtm_softmax_xent_mix(const void* logits, int logits_bf16, const int*
   else
     hipLaunchKernelGGL(softmax_xent_mix_kernel<float>, dim3(B), dim3(256), 0, (hipStream_t)stream,
                        (const float*)logits, labels, plan, loss, (float*)dlogits, K, smoothing, gscale, ldx);
+  return 0;
+}
+
+// The distillation loss of the main head (softmax_xent_body<T, MIX, true>): teacher is a [B][K] block of the
+// student's dtype at pitch ldt, read in place like the student's at ldx; plan null: one label per row, else the
+// two-label target of dtm_softmax_xent_mix.  kl (optional) receives the row's unweighted KL(q || pT).  Returns -1 for
+// a bad pointer or size, -2 for temperature <= 0 or alpha outside [0, 1] (NaN included); nothing is launched then.
+template <typename T>
+static void launch_xent_distill(const void* logits, const void* teacher, int ldt, const int* labels, const int* plan,
+                                float* loss, float* kl, void* dlogits, int B, int K, float smoothing, float alpha,
+                                float temperature, float gscale, int ldx, hipStream_t stream) {
+  if (plan)
+    hipLaunchKernelGGL((softmax_xent_distill_kernel<T, true>), dim3(B), dim3(256), 0, stream, (const T*)logits,
+                       (const T*)teacher, ldt, labels, plan, loss, kl, (T*)dlogits, K, smoothing, alpha, temperature,
+                       gscale, ldx);
+  else
+    hipLaunchKernelGGL((softmax_xent_distill_kernel<T, false>), dim3(B), dim3(256), 0, stream, (const T*)logits,
+                       (const T*)teacher, ldt, labels, plan, loss, kl, (T*)dlogits, K, smoothing, alpha, temperature,
+                       gscale, ldx);
+}
+
+DTM_API int dtm_softmax_xent_distill(const void* logits, int logits_bf16, const void* teacher, int ldt,
+                                     const int* labels, const int* plan, float* loss, float* kl, void* dlogits, int B,
+                                     int K, float smoothing, float alpha, float temperature, float gscale, int ldx,
+                                     void* stream) {
+  if (!logits || !teacher || !labels || !loss || B < 1 || B > 65535 || K < 1) return -1;
+  if (!(temperature > 0.f) || !(alpha >= 0.f && alpha <= 1.f)) return -2;
+  if (ldx < K) ldx = K;
+  if (ldt < K) ldt = K;
+  if (logits_bf16)
+    launch_xent_distill<bf16_t>(logits, teacher, ldt, labels, plan, loss, kl, dlogits, B, K, smoothing, alpha,
+                                temperature, gscale, ldx, (hipStream_t)stream);
+  else
+    launch_xent_distill<float>(logits, teacher, ldt, labels, plan, loss, kl, dlogits, B, K, smoothing, alpha,
+                               temperature, gscale, ldx, (hipStream_t)stream);
   return 0;
 }
 

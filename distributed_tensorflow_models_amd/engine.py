@@ -117,13 +117,27 @@ def _stage(static, new):
         static.copy_(new, non_blocking=True)
 
 
+class DistillConfig:
+    """Knowledge distillation for TrainStep: ``teacher`` (a model of the zoo, already holding its trained weights)
+    is frozen and run in inference mode on every micro-batch; the main head's loss becomes
+    (1 - alpha) * hard + alpha * temperature^2 * KL(softmax(teacher / T) || softmax(student / T))."""
+    __slots__ = ("teacher", "alpha", "temperature")
+
+    def __init__(self, teacher, alpha=0.5, temperature=4.0):
+        if not isinstance(teacher, torch.nn.Module):
+            raise ValueError("the distillation teacher must be a torch.nn.Module, got %r" % (teacher,))
+        F.Distill(torch.zeros(1, 1), alpha, temperature)  # its checks of alpha and temperature
+        self.teacher, self.alpha, self.temperature = teacher, float(alpha), float(temperature)
+
+
 class TrainStep:
     def __init__(self, model, optimizer="momentum", lr=0.1, momentum=0.9, rho=0.9, epsilon=None, bucket_mb=32.0,
                  label_smoothing=0.0, aux_weight=0.4, ema_decay=None, lr_schedule=None, use_graph=False,
                  process_group=None, weight_decay=None, batch_weight=1.0, nan_guard=True, timer=None,
                  grad_comm_dtype=None, ema_buffers=True, bn_sync_every=1, wgrad_stream=None, bsp_check=None,
                  overlap=True, force_comm=False, graph_comm=False, lars_eeta=0.001, lars_epsilon=0.0,
-                 clip_global_norm=None, beta1=0.9, beta2=0.999, accum_steps=1, mix=None, rank=None):
+                 clip_global_norm=None, beta1=0.9, beta2=0.999, accum_steps=1, mix=None, rank=None,
+                 distill=None):
         # epsilon None: the optimizer's own default (1e-10; Adam 1e-8); beta1 / beta2: Adam only
         # accum_steps N: a call runs N micro-batches, sums their gradients (parallel/bsp.py begin_micro /
         # accumulate) and applies ONE update: an effective batch of N times the micro-batch on the same memory
@@ -131,7 +145,26 @@ class TrainStep:
         # a buffer this step owns and the loss takes both labels; the plan of micro-batch i of step s is
         # sample_plan(mix, rank, s, i, ...).  None: nothing is constructed, today's launches and bits.
         # rank: the rank the plans are drawn for (default: the process group's)
+        # distill: a DistillConfig - its frozen teacher runs (no grad, inference mode) on every micro-batch the
+        # student sees, mixed ones included, and the main head's loss takes its logits (ops.nn.Distill).  The teacher
+        # belongs to nothing below: not the optimizer's tables, the buckets, the BN sync or the EMA rows.  None:
+        # nothing is constructed, today's launches and bits.
         self.model = model
+        if distill is not None and not isinstance(distill, DistillConfig):
+            raise ValueError("distill must be an engine.DistillConfig or None, got %r" % (distill,))
+        self.distill = distill
+        self._kl_rows = []  # per micro-batch of the last step: the device KL rows of the loss
+        if distill is not None:
+            if distill.teacher is model or any(m is model for m in distill.teacher.modules()) \
+                    or any(m is distill.teacher for m in model.modules()):
+                raise ValueError("the distillation teacher must be a network of its own, not (part of) the student")
+            distill.teacher.requires_grad_(False)
+            first = next(model.parameters(), None)
+            if first is not None:
+                distill.teacher.to(first.device)
+            # its bf16 compute copies, once: no optimizer owns them, so nothing rewrites them (the process-wide
+            # refresh of the dgrad copies after an update re-derives a registered copy from these same bits)
+            prepare_compute_copies(distill.teacher)
         if mix is not None and not isinstance(mix, _mix.MixConfig):
             raise ValueError("mix must be an ops.mix.MixConfig or None, got %r" % (mix,))
         self.mix = mix
@@ -193,15 +226,35 @@ class TrainStep:
         if self.dp.world > 1 and params and params[0].is_cuda:
             _lib.set_reserved_cus(reserved_cus_default())
 
-    def loss_fn(self, out, labels, plan=None):
+    def loss_fn(self, out, labels, plan=None, teacher_logits=None):
         aux = None
         if isinstance(out, tuple):
             out, aux = out
         bw = self.batch_weight
         heads = [(out, bw)] + ([(aux, self.aux_weight * bw)] if aux is not None and self.aux_weight else [])
+        if teacher_logits is not None:
+            loss = F.mean_xent_loss(heads, labels, self.smoothing, mix=plan, distill=F.Distill(
+                teacher_logits, self.distill.alpha, self.distill.temperature))
+            self._kl_rows.append(F.mean_xent_loss.kl_rows)
+            return loss
         if plan is None:
             return F.mean_xent_loss(heads, labels, self.smoothing)
         return F.mean_xent_loss(heads, labels, self.smoothing, mix=plan)
+
+    # ---- knowledge distillation --------------------------------------------------------------
+    def _teacher_logits(self, images):
+        """The frozen teacher's main-head logits on the batch the student is about to see."""
+        with torch.no_grad():
+            out = self.distill.teacher(images, training=False)
+        return out[0] if isinstance(out, tuple) else out
+
+    def last_distill_kl(self):
+        """Mean over the last step's rows (all its micro-batches) of KL(teacher || student) at the temperature,
+        unweighted.  Reads the device: call on logged steps only.  None without distillation or before the first
+        step."""
+        if not self._kl_rows:
+            return None
+        return float(torch.cat([k.detach().float().reshape(-1) for k in self._kl_rows]).mean())
 
     # ---- mixup / CutMix (ops/mix.py) ---------------------------------------------------------
     def _draw_plans(self, images):
@@ -268,6 +321,8 @@ class TrainStep:
         micro = list(zip(images, labels)) if isinstance(images, (list, tuple)) else [(images, labels)]
         n = len(micro)
         losses = []
+        if self.distill is not None:
+            self._kl_rows = []
         for i, (images, labels) in enumerate(micro):
             last = i == n - 1
             self.dp.begin_micro(i, n)
@@ -280,10 +335,17 @@ class TrainStep:
                 if plans is not None:
                     with roctx("mix"):
                         images = self._mixed(images, plans[i])
+                tz = None
+                if self.distill is not None:
+                    with roctx("teacher"):
+                        tz = self._teacher_logits(images)
                 with roctx("forward"):
                     out = self.model(images, training=True)
                 with roctx("loss"):
-                    loss = self.loss_fn(out, labels) if plans is None else self.loss_fn(out, labels, plans[i])
+                    if tz is not None:
+                        loss = self.loss_fn(out, labels, plans[i] if plans is not None else None, tz)
+                    else:
+                        loss = self.loss_fn(out, labels) if plans is None else self.loss_fn(out, labels, plans[i])
                 if last:
                     self._mark("fwd")
                     self.bufsync.issue()  # forward has finished every moving-statistics update

@@ -103,7 +103,8 @@ _SIGS = {
     "dtm_global_avg_bwd_bf16": (None, [_P, _P, _I, _I, _I, _P]),
     "dtm_softmax_xent": (None, [_P, _I, _P, _P, _P, _I, _I, _F, _F, _P, _I, _P]),
     "dtm_softmax_xent_mix": (_I, [_P, _I, _P, _P, _P, _P, _I, _I, _F, _F, _I, _P]),
-    "dtm_mix_images": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "dtm_softmax_xent_distill": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _I, _F, _F, _F, _F, _I, _P]),
+    "dtm_mix_images":(_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "dtm_opt_chunk_size": (_I, []),
     "dtm_opt_tensor_bytes": (_I, []),
     "dtm_opt_chunk_bytes": (_I, []),

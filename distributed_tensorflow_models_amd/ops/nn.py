@@ -940,19 +940,136 @@ class _MeanXentMixFn(torch.autograd.Function):
         return (None, None, None, None) + tuple(_scaled_rows_grad(dl, gl) for dl in ctx.saved_tensors)
 
 
-def mean_xent_loss(heads, labels, smoothing=0.0, mix=None):
+class Distill:
+    """The soft-target term of a knowledge-distillation loss (Hinton, Vinyals, Dean 2015) for mean_xent_loss:
+    ``teacher_logits`` [B, K] of the frozen teacher on the student's batch (no gradient flows to it), the weight
+    ``alpha`` in [0, 1] of the soft term and its ``temperature`` > 0."""
+    __slots__ = ("teacher_logits", "alpha", "temperature")
+
+    def __init__(self, teacher_logits, alpha=0.5, temperature=4.0):
+        alpha, temperature = float(alpha), float(temperature)
+        if not 0.0 <= alpha <= 1.0:
+            raise ValueError("distillation alpha must lie in [0, 1], got %r" % (alpha,))
+        if not (0.0 < temperature < float("inf")):
+            raise ValueError("distillation temperature must be positive and finite, got %r" % (temperature,))
+        if not isinstance(teacher_logits, torch.Tensor) or teacher_logits.dim() != 2:
+            raise ValueError("distillation needs teacher logits of shape [B, K]")
+        self.teacher_logits, self.alpha, self.temperature = teacher_logits, alpha, temperature
+
+
+class _MeanXentDistillFn(torch.autograd.Function):
+    """_MeanXentFn / _MeanXentMixFn with the distillation term on head 0 (dtm_softmax_xent_distill: one launch gives the
+    head's per-row (1 - a) * hard + a * T^2 * KL, its gradient and the per-row KL); further heads keep their plain or
+    mixed hard loss.  The combine launch and the backward are _MeanXentFn's.  ``kl_rows`` is the fp32 [B] KL of the
+    last forward (logging)."""
+    kl_rows = None
+
+    @staticmethod
+    def forward(ctx, labels, plan_dev, teacher, alpha, temperature, smoothing, weights, *logits):
+        L = _lib.lib()
+        B = labels.shape[0]
+        lab = labels.to(torch.int32).contiguous()
+        losses = torch.empty((len(logits), B), device=lab.device, dtype=torch.float32)
+        kl = torch.empty((B,), device=lab.device, dtype=torch.float32)
+        dls = []
+        for i, (lg, w) in enumerate(zip(logits, weights)):
+            lg, ld = _rows(lg)
+            bf = int(lg.dtype == torch.bfloat16)
+            dl = torch.empty(lg.shape, device=lg.device, dtype=lg.dtype)
+            if i == 0:
+                tz, ldt = _rows(teacher if teacher.dtype == lg.dtype else teacher.to(lg.dtype))
+                _check(L.dtm_softmax_xent_distill(_lib.ptr(lg), bf, _lib.ptr(tz), ldt, _lib.ptr(lab),
+                                                  _lib.ptr(plan_dev) if plan_dev is not None else None,
+                                                  _lib.ptr(losses[i]), _lib.ptr(kl), _lib.ptr(dl), B, lg.shape[1],
+                                                  float(smoothing), float(alpha), float(temperature), float(w) / B, ld,
+                                                  _lib.stream_ptr()), "softmax_xent_distill")
+            elif plan_dev is not None:
+                _check(L.dtm_softmax_xent_mix(_lib.ptr(lg), bf, _lib.ptr(lab), _lib.ptr(plan_dev), _lib.ptr(losses[i]),
+                                              _lib.ptr(dl), B, lg.shape[1], float(smoothing), float(w) / B, ld,
+                                              _lib.stream_ptr()), "softmax_xent_mix")
+            else:
+                L.dtm_softmax_xent(_lib.ptr(lg), bf, _lib.ptr(lab), _lib.ptr(losses[i]), _lib.ptr(dl), B, lg.shape[1],
+                                   float(smoothing), float(w) / B, None, ld, _lib.stream_ptr())
+            dls.append(dl)
+        out = torch.empty((), device=lab.device, dtype=torch.float32)
+        ws = (ctypes.c_float * len(weights))(*[float(w) / B for w in weights])
+        _check(L.dtm_loss_combine(_lib.ptr(losses), len(logits), B, ctypes.cast(ws, ctypes.c_void_p), _lib.ptr(out),
+                                  _lib.stream_ptr()), "loss_combine")
+        _MeanXentDistillFn.kl_rows = kl
+        ctx.save_for_backward(*dls)
+        return out
+
+    @staticmethod
+    def backward(ctx, gl):
+        gl = gl.float().reshape(1).contiguous()
+        return (None,) * 7 + tuple(_scaled_rows_grad(dl, gl) for dl in ctx.saved_tensors)
+
+
+def _mixed_rows(lg, labels, smoothing, mix, wl, partner_labels):
+    """Per-row hard loss of one head: plain, or the two-label form of a MixPlan."""
+    la = softmax_cross_entropy(lg, labels, smoothing)
+    if mix is None:
+        return la
+    return wl * la + (1.0 - wl) * softmax_cross_entropy(lg, partner_labels, smoothing)
+
+
+def distill_rows(logits, teacher_logits, temperature):
+    """Per-row KL(softmax(z / T) || softmax(s / T)) in fp32 from torch ops: the documented oracle of the soft term
+    (and the CPU path).  The teacher is detached."""
+    s = logits.float() / temperature
+    z = teacher_logits.detach().float() / temperature
+    log_q = torch.log_softmax(z, -1)
+    return (torch.softmax(z, -1) * (log_q - torch.log_softmax(s, -1))).sum(-1)
+
+
+def mean_xent_loss(heads, labels, smoothing=0.0, mix=None, distill=None):
     """sum over (logits, weight) heads of weight * mean softmax cross-entropy (the training loss with Inception's
     weighted aux head); one fused op on the GPU, the plain composition elsewhere.  ``mix``: the batch's MixPlan
     (ops/mix.py) - row r's loss is w_lab[r] * xent(labels[r]) + (1 - w_lab[r]) * xent(labels[partner[r]]), i.e. the
-    cross-entropy against the mix of the two labels' (smoothed) targets."""
+    cross-entropy against the mix of the two labels' (smoothed) targets.  ``distill``: a Distill record - head 0's row
+    loss becomes (1 - a) * hard + a * T^2 * KL(softmax(z / T) || softmax(s / T)) with z the teacher's logits; further
+    heads keep their hard loss.  ``mean_xent_loss.kl_rows`` then holds the per-row KL (fp32 [B]) of the last call."""
     heads = [(lg, float(w)) for lg, w in heads]
     ok = all(lg.is_cuda and lg.dim() == 2 and lg.dtype in (torch.float32, torch.bfloat16) for lg, _ in heads)
     ok = ok and labels.is_cuda and 1 <= len(heads) <= 4 and labels.shape[0] <= 65535
+    if distill is not None:
+        if not isinstance(distill, Distill):
+            raise ValueError("distill must be an ops.nn.Distill or None, got %r" % (distill,))
+        tz = distill.teacher_logits
+        if tuple(tz.shape) != tuple(heads[0][0].shape):
+            raise ValueError("teacher logits of shape %r against student logits of shape %r"
+                             % (tuple(tz.shape), tuple(heads[0][0].shape)))
+    plan_dev = None
     if mix is not None:
         if mix.B != labels.shape[0]:
             raise ValueError("mixing plan of %d rows used on %d labels" % (mix.B, labels.shape[0]))
         mix.validate()  # the host copy, before anything is launched: the kernel trusts the device copy
         if ok and mix.dev is not None and mix.dev.device == labels.device:
+            plan_dev = mix.dev
+    if distill is not None:
+        if ok and tz.device == labels.device and (mix is None or plan_dev is not None):
+            out = _MeanXentDistillFn.apply(labels, plan_dev, tz.detach(), distill.alpha, distill.temperature,
+                                           float(smoothing), [w for _, w in heads], *[lg for lg, _ in heads])
+            mean_xent_loss.kl_rows = _MeanXentDistillFn.kl_rows
+            return out
+        wl = partner_labels = None
+        if mix is not None:
+            wl = torch.from_numpy(mix.w_lab.copy()).to(labels.device)
+            partner_labels = labels[torch.from_numpy(mix.partner.astype("int64")).to(labels.device)]
+        a, T = distill.alpha, distill.temperature
+        loss = None
+        for i, (lg, w) in enumerate(heads):
+            rows = _mixed_rows(lg, labels, smoothing, mix, wl, partner_labels)
+            if i == 0:
+                kl = distill_rows(lg, tz.to(lg.device), T)
+                mean_xent_loss.kl_rows = kl.detach()
+                rows = (1.0 - a) * rows + (a * T * T) * kl  # (a == 0: 1 * rows + 0 * kl, the hard loss's bits)
+            term = rows.mean()
+            term = term if w == 1.0 else w * term
+            loss = term if loss is None else loss + term
+        return loss
+    if mix is not None:
+        if plan_dev is not None:
             return _MeanXentMixFn.apply(labels, mix.dev, float(smoothing), [w for _, w in heads],
                                         *[lg for lg, _ in heads])
         wl = torch.from_numpy(mix.w_lab.copy()).to(labels.device)
@@ -973,6 +1090,9 @@ def mean_xent_loss(heads, labels, smoothing=0.0, mix=None):
         term = term if w == 1.0 else w * term
         loss = term if loss is None else loss + term
     return loss
+
+
+mean_xent_loss.kl_rows = None
 
 
 # ---------------------------------------------------------------------------------------------

@@ -120,6 +120,37 @@ MIX_BSP_ONLY = ("--mixup_alpha / --cutmix_alpha need --sync_mode bsp (got %s): t
                 "step, which under asp / ssp is no property of a worker's own batch sequence")
 
 
+DISTILL_BSP_ONLY = ("--distill_teacher needs --sync_mode bsp (got %s): under asp / ssp the step is the parameter "
+                    "store's, which has no place for a second network's forward")
+
+
+def parse_model_kw(text):
+    """"k=v,..." -> {k: int or float}: the numeric model keywords of --distill_teacher_kw."""
+    out = {}
+    for item in (t.strip() for t in text.split(",")):
+        if not item:
+            continue
+        k, sep, v = item.partition("=")
+        try:
+            if not sep or not k.strip():
+                raise ValueError(item)
+            out[k.strip()] = int(v) if v.strip().lstrip("+-").isdigit() else float(v)
+        except ValueError:
+            raise ValueError("--distill_teacher_kw takes numeric k=v pairs, got %r" % item) from None
+    return out
+
+
+def distill_checkpoint_path(path):
+    """The checkpoint prefix --distill_checkpoint names: a prefix itself, or a directory's newest checkpoint."""
+    from .ckpt.saver import latest_checkpoint
+    if path and os.path.isdir(path):
+        path = latest_checkpoint(path) or ""
+    if not path or not os.path.exists(path + ".index"):
+        raise ValueError("--distill_teacher needs --distill_checkpoint, a checkpoint (or a directory holding one) of "
+                         "the trained teacher; got %r" % (path,))
+    return path
+
+
 def define_common_flags(flags, preset):
     """Flags shared by every trainer (reference flag inventory) + MI355X extras."""
     p = PRESETS[preset]
@@ -172,6 +203,16 @@ def define_common_flags(flags, preset):
             ("mix_prob", Fl, 1.0, "probability that a batch (a row with --mix_per_row) is mixed at all"),
             ("mix_switch_prob", Fl, 0.5, "with both alphas above 0: the probability of CutMix over mixup"),
             ("mix_per_row", B, False, "draw kind, weight and box per row instead of per batch"),
+            # knowledge distillation (engine.DistillConfig; BSP only)
+            ("distill_teacher", S, "", "nets_factory name of a frozen teacher network, built with the student's "
+             "number of classes ('' = off)"),
+            ("distill_teacher_kw", S, "", "numeric model keywords of the teacher, 'k=v,...' (e.g. resnet_size=8)"),
+            ("distill_checkpoint", S, "", "the trained teacher's checkpoint, or a directory holding one (required "
+             "with --distill_teacher)"),
+            ("distill_teacher_ema", B, False, "restore the teacher from the checkpoint's EMA shadows"),
+            ("distill_teacher_scope", S, "", "variable-scope prefix of the teacher's names in its checkpoint"),
+            ("distill_alpha", Fl, 0.5, "weight of the soft-target term, in [0, 1]"),
+            ("distill_temperature", Fl, 4.0, "temperature of the soft targets"),
             # MI355X-native extras
             ("sync_mode", S, "", "bsp | asp | ssp (default from the entry script)"),
             ("max_staleness", I, 5, "SSP staleness bound in local steps"),
@@ -288,6 +329,18 @@ def train(preset, flags, default_mode="bsp"):
         from .ops.mix import MixConfig
         mix_cfg = MixConfig(FLAGS.mixup_alpha, FLAGS.cutmix_alpha, FLAGS.mix_prob, FLAGS.mix_switch_prob,
                             FLAGS.mix_per_row, seed=FLAGS.seed)
+    distill_ckpt = distill_kw = None
+    if FLAGS.distill_teacher:
+        if mode in ("asp", "ssp"):
+            raise ValueError(DISTILL_BSP_ONLY % mode)
+        if FLAGS.distill_teacher not in nets_factory.networks_map:
+            raise ValueError("--distill_teacher: unknown network %r" % FLAGS.distill_teacher)
+        if not 0.0 <= FLAGS.distill_alpha <= 1.0:
+            raise ValueError("--distill_alpha must lie in [0, 1], got %r" % FLAGS.distill_alpha)
+        if not 0.0 < FLAGS.distill_temperature < float("inf"):
+            raise ValueError("--distill_temperature must be positive, got %r" % FLAGS.distill_temperature)
+        distill_kw = parse_model_kw(FLAGS.distill_teacher_kw)
+        distill_ckpt = distill_checkpoint_path(FLAGS.distill_checkpoint)
     ps_hosts = [h for h in FLAGS.ps_hosts.split(",") if h]
     worker_hosts = [h for h in FLAGS.worker_hosts.split(",") if h]
     if FLAGS.job_name == "ps":
@@ -374,6 +427,21 @@ def train(preset, flags, default_mode="bsp"):
         # from the fine-tune values (a restore after them would be folded into the next BN sync as a W-fold delta)
         ft = [v for v in model_variables(model, None, None, prefix=ckpt_kw["prefix"])]
         ft_missing = Saver(ft).restore(FLAGS.fine_tune_checkpoint, strict=False)
+    distill_cfg = None
+    if distill_ckpt:
+        # the frozen teacher: built with the student's classes, restored as an evaluator restores (EMA shadows on
+        # request), and handed to the step; it is in none of the variable lists below, so no checkpoint holds it
+        from .engine import DistillConfig
+        from .evaluator import restore_for_eval
+        teacher = nets_factory.build(FLAGS.distill_teacher, num_classes=cfg["num_classes"], **distill_kw).to(device)
+        restore_for_eval(teacher, distill_ckpt, FLAGS.distill_teacher_ema, prefix=FLAGS.distill_teacher_scope)
+        t_size = nets_factory.default_image_size(FLAGS.distill_teacher)
+        if t_size != cfg["image_size"]:
+            logging.warning("the teacher %s is built for %d x %d images and is fed the student's %d x %d batches as "
+                            "they are", FLAGS.distill_teacher, t_size, t_size, cfg["image_size"], cfg["image_size"])
+        distill_cfg = DistillConfig(teacher, FLAGS.distill_alpha, FLAGS.distill_temperature)
+        logging.info("distilling from %s (%s), alpha %g, temperature %g", FLAGS.distill_teacher, distill_ckpt,
+                     FLAGS.distill_alpha, FLAGS.distill_temperature)
     if mode == "bsp":
         if FLAGS.use_hipgraph and world > 1:
             logging.warning("--use_hipgraph ignored: step capture is single-rank only (world size %d)", world)
@@ -387,7 +455,7 @@ def train(preset, flags, default_mode="bsp"):
                             else None, lars_eeta=FLAGS.lars_eeta, lars_epsilon=FLAGS.lars_epsilon,
                             clip_global_norm=FLAGS.clip_global_norm if FLAGS.clip_global_norm > 0 else None,
                             beta1=FLAGS.adam_beta1, beta2=FLAGS.adam_beta2, accum_steps=accum, mix=mix_cfg, rank=rank,
-                            **opt_kw)
+                            distill=distill_cfg, **opt_kw)
         vars_ = model_variables(model, step_fn.opt, gstep, **ckpt_kw)
         vars_[-1].name = cfg.get("global_step_name", "global_step")
         if path:
@@ -550,6 +618,8 @@ def train(preset, flags, default_mode="bsp"):
                 extra["adam_step"] = step_fn.opt.adam_step()  # applied updates: lags global_step after a NaN skip
             if mix_cfg is not None and metrics.f is not None:
                 extra["mix_lambda"] = step_fn.last_mix_lambda()  # mean own-label weight of this step (a host value)
+            if distill_cfg is not None and metrics.f is not None:
+                extra["distill_kl"] = step_fn.last_distill_kl()  # a device read, after the synchronisation above
             if metrics.f is not None and getattr(mkw.get("quantize"), "fused", False):
                 # device reads, after the logged step's synchronisation above
                 from .ops import fakequant

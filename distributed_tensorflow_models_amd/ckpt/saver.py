@@ -9,7 +9,10 @@
   ``<v>/RMSProp``, ``<v>/RMSProp_1``; Adam ``<v>/Adam`` (m), ``<v>/Adam_1`` (v) and the scalars ``beta1_power``,
   ``beta2_power`` = b^(t+1) after t applied updates, from which a restore recovers t (parity of these names with a
   file written by TensorFlow itself is not checked either); EMA shadows
-  ``<v>/ExponentialMovingAverage``; ``global_step`` int64;
+  ``<v>/ExponentialMovingAverage``; ``global_step`` int64; for a pruned ``<scope>/weights`` (ops/prune.py)
+  ``<scope>/mask`` (float32, the weight's shape and layout) and ``<scope>/threshold`` (a float32 scalar holding the
+  bit pattern of the threshold key), optional on restore (parity of these names with a file written by
+  TensorFlow's model_pruning is not checked either);
 * ``max_to_keep`` retention; writes are atomic (tempstate + rename in the native writer);
 * the ``.meta`` GraphDef is not produced (there is no TF graph) - documented deviation.
 """
@@ -81,8 +84,55 @@ class AdamPowerVar(TFVar):
         self.optimizer._adam_loaded["beta%d_power" % (self.which + 1)] = float(self.tensor)
 
 
+class MaskVar(TFVar):
+    """``<scope>/mask`` of a pruned variable: float32 zeros and ones of the weight's shape in its TF layout, formed
+    from the pruner's mask bytes when the variable is saved (``refresh``) and written back into them on load.  A
+    checkpoint without it leaves the mask as it is (``optional``): all ones on a fresh start."""
+    __slots__ = ("pruner", "index")
+    optional = True
+
+    def __init__(self, name, pruner, index, layout=None, partitions=None):
+        TFVar.__init__(self, name, pruner.masks[index], layout, partitions)
+        self.pruner, self.index = pruner, index
+
+    def refresh(self):
+        self.tensor = self.pruner.masks[self.index].float()
+
+    def export(self):
+        self.refresh()
+        return TFVar.export(self)
+
+    def load(self, arr):
+        self.tensor = torch.empty(self.pruner.masks[self.index].shape, dtype=torch.float32)
+        TFVar.load(self, arr)
+        with torch.no_grad():
+            self.pruner.masks[self.index].copy_(self.tensor != 0)
+
+
+class ThresholdVar(TFVar):
+    """``<scope>/threshold`` of a pruned variable: a float32 scalar with the bit pattern of the threshold key."""
+    __slots__ = ("pruner", "index")
+    optional = True
+
+    def __init__(self, name, pruner, index):
+        TFVar.__init__(self, name, torch.zeros((), dtype=torch.float32))
+        self.pruner, self.index = pruner, index
+
+    def refresh(self):
+        self.tensor = self.pruner.tau[self.index:self.index + 1].cpu().view(torch.float32).reshape(())
+
+    def export(self):
+        self.refresh()
+        return TFVar.export(self)
+
+    def load(self, arr):
+        TFVar.load(self, arr)
+        with torch.no_grad():
+            self.pruner.tau[self.index:self.index + 1].copy_(self.tensor.reshape(1).view(torch.int32))
+
+
 def model_variables(model, optimizer=None, global_step=None, include_slots=True, prefix="", partitions=None,
-                    store=None):
+                    store=None, pruner=None):
     """Collect TFVar records for a model built from models.layers (+ optimizer slots / EMA).
 
     prefix: the trainer's variable_scope ('partitioned_space/', 'root/'); partitions: P of its
@@ -118,6 +168,14 @@ def model_variables(model, optimizer=None, global_step=None, include_slots=True,
         if optimizer.kind == "adam":
             out.append(AdamPowerVar(prefix + "beta1_power", optimizer, 0))
             out.append(AdamPowerVar(prefix + "beta2_power", optimizer, 1))
+    if pruner is not None:
+        from ..ops.prune import mask_scope
+        for i, p in enumerate(pruner.params):
+            base = by_param.get(id(p))
+            if base is None:
+                continue
+            out.append(MaskVar(mask_scope(base.name) + "/mask", pruner, i, base.layout, partitions))
+            out.append(ThresholdVar(mask_scope(base.name) + "/threshold", pruner, i))
     if store is not None and include_slots:
         # ASP / SSP: the slots live in the owner shards (every rank maps every shard)
         for i, p in enumerate(store.params):
@@ -217,7 +275,7 @@ class Saver:
         on the current stream; returns (arrays-producer, event)."""
         host = []
         for v in self.vars:
-            if isinstance(v, AdamPowerVar):
+            if isinstance(v, (AdamPowerVar, MaskVar, ThresholdVar)):
                 v.refresh()
             t = v.tensor.detach()
             if v.layout == "KRSC->HWIO":
@@ -304,7 +362,7 @@ class Saver:
             for v in self.vars:
                 if r.has_tensor(v.name):
                     v.load(r.get_tensor(v.name))
-                else:
+                elif not getattr(v, "optional", False):
                     missing.append(v.name)
         finally:
             r.close()

@@ -14,7 +14,9 @@ from .ops import elementwise as _elementwise
 from .ops import fused as _fused
 from .ops import mix as _mix
 from .ops import nn as F
+from .ops import prune as _prune
 from .ops.optim import FusedOptimizer
+from .ops.prune import PruneConfig  # noqa: F401  (TrainStep(prune=PruneConfig(...)))
 from .parallel.bsp import BSPDataParallel, BufferSync
 from .utils.profiler import range_pop, range_push, roctx
 
@@ -137,7 +139,7 @@ class TrainStep:
                  grad_comm_dtype=None, ema_buffers=True, bn_sync_every=1, wgrad_stream=None, bsp_check=None,
                  overlap=True, force_comm=False, graph_comm=False, lars_eeta=0.001, lars_epsilon=0.0,
                  clip_global_norm=None, beta1=0.9, beta2=0.999, accum_steps=1, mix=None, rank=None,
-                 distill=None):
+                 distill=None, prune=None):
         # epsilon None: the optimizer's own default (1e-10; Adam 1e-8); beta1 / beta2: Adam only
         # accum_steps N: a call runs N micro-batches, sums their gradients (parallel/bsp.py begin_micro /
         # accumulate) and applies ONE update: an effective batch of N times the micro-batch on the same memory
@@ -149,6 +151,15 @@ class TrainStep:
         # student sees, mixed ones included, and the main head's loss takes its logits (ops.nn.Distill).  The teacher
         # belongs to nothing below: not the optimizer's tables, the buckets, the BN sync or the EMA rows.  None:
         # nothing is constructed, today's launches and bits.
+        # prune: an ops.prune.PruneConfig - gradual magnitude pruning.  After the optimizer's launch of step t (=
+        # global_step at entry) the masks are re-selected when prune.updates_at(t), on the updated weights with the
+        # masks so far applied (so a mask only shrinks), and on every step the masks are applied to the weights,
+        # their bf16 copies and EMA shadows, before the dgrad copies are re-derived.  Neither pass looks at the skip
+        # flag.  None: nothing is constructed, today's launches and bits.
+        if prune is not None and not isinstance(prune, PruneConfig):
+            raise ValueError("prune must be an ops.prune.PruneConfig or None, got %r" % (prune,))
+        self.prune = prune
+        self.pruner = None
         self.model = model
         if distill is not None and not isinstance(distill, DistillConfig):
             raise ValueError("distill must be an engine.DistillConfig or None, got %r" % (distill,))
@@ -203,6 +214,11 @@ class TrainStep:
                                   if (ema_decay is not None and ema_buffers) else (),
                                   lars_eeta=lars_eeta, lars_epsilon=lars_epsilon, clip_global_norm=clip_global_norm,
                                   beta1=beta1, beta2=beta2)
+        if prune is not None:
+            pruned = [(name, p) for name, p in model.named_parameters() if p.requires_grad and prune.selects(name, p)]
+            self.pruner = _prune.Pruner([(name, p.data, getattr(p, "bf16", None), self.opt.state[p].get("ema"))
+                                         for name, p in pruned])
+            self.pruner.params = [p for _name, p in pruned]  # for the checkpoint's <scope>/mask, <scope>/threshold
         if rank is None:
             import torch.distributed as dist
             rank = dist.get_rank(process_group) if dist.is_available() and dist.is_initialized() else 0
@@ -410,11 +426,30 @@ class TrainStep:
             return [0] * self.accum_steps
         return [int(v) for v in self.dp.micro_flags.tolist()]
 
+    # ---- gradual magnitude pruning (ops/prune.py) -----------------------------------------------
+    def _prune_stage(self):
+        t = self.global_step
+        self.pruner.stage(self.prune.sparsity_at(t), self.prune.updates_at(t))
+
+    def last_sparsity(self):
+        """(achieved, target): the achieved sparsity (sum n - sum kept) / sum n over the pruned tensors and the
+        schedule's value at the last step.  Reads the device: call on logged steps only.  None without pruning."""
+        if self.pruner is None:
+            return None
+        return self.pruner.sparsity(), self.prune.sparsity_at(max(self.global_step - 1, 0))
+
     def _eager_step(self, images, labels):
         rng = range_push("train_step")
         loss, skip = self._forward_backward(images, labels)
         with roctx("optimizer"):
-            self.opt.step(self.current_lr(), grad_scale=self.dp.grad_scale, skip_flag=skip)
+            if self.pruner is None:
+                self.opt.step(self.current_lr(), grad_scale=self.dp.grad_scale, skip_flag=skip)
+            else:
+                self.opt.step(self.current_lr(), grad_scale=self.dp.grad_scale, skip_flag=skip, refresh=False)
+                self._prune_stage()
+                self.pruner.launch()
+                if self.opt._dev is not None:
+                    F.refresh_flipped()
         self._mark("optimizer")
         self.global_step += 1
         range_pop(rng)
@@ -456,6 +491,8 @@ class TrainStep:
                 with torch.cuda.graph(g):
                     loss, skip = self._forward_backward(self._static_x, self._static_y, self._static_plans)
                     self.opt.launch(skip)
+                    if self.pruner is not None:  # what it does is data in its device record, staged per replay
+                        self.pruner.launch()
                     from .ops.nn import refresh_flipped
                     refresh_flipped()
             finally:
@@ -470,6 +507,8 @@ class TrainStep:
                 for static, plan in zip(self._static_plans, self._draw_plans(images)):
                     static.dev.copy_(plan.host_tensor(pin=True), non_blocking=True)
         self.opt.set_dynamic(self.current_lr(), self.dp.grad_scale)
+        if self.pruner is not None:
+            self._prune_stage()
         self._graph.replay()
         self.opt.num_updates += 1
         self.global_step += 1

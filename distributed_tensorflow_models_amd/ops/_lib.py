@@ -117,6 +117,16 @@ _SIGS = {
     "dtm_multi_tensor_adam": (_I, [_P, _P, _I, _D, _D, _D, _I, _P, _P, _P, _P, _P]),
     "dtm_check_finite": (None, [_P, _L, _P, _P]),
     "dtm_grad_accum": (_I, [_P, _P, _L, _I, _P, _P]),
+    "dtm_prune_tensor_bytes": (_I, []),
+    "dtm_prune_chunk_bytes": (_I, []),
+    "dtm_prune_rec_bytes": (_I, []),
+    "dtm_prune_chunk_size": (_I, []),
+    "dtm_prune_hist_bins": (_I, []),
+    "dtm_prune_num_chunks": (_L, [_P, _L]),
+    "dtm_prune_fill_record": (_I, [_P, _D, _I]),
+    "dtm_prune_hist_stage": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _I, _L, _P]),
+    "dtm_prune_select": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _L, _P]),
+    "dtm_prune_apply": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _L, _I, _P]),
     "dtm_f32_to_bf16": (None, [_P, _P, _L, _P]),
     "dtm_scale": (None, [_P, _L, _F, _P]),
     "dtm_bn_apply_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _P]),

@@ -321,13 +321,16 @@ class FusedOptimizer:
         self._adam_loaded = {}
         self.set_adam_step(int(global_step) if t is None else t)
 
-    def step(self, lr=None, grad_scale=1.0, skip_flag=None):
+    def step(self, lr=None, grad_scale=1.0, skip_flag=None, refresh=True):
+        """``refresh`` False: the caller re-derives the dgrad copies itself (``ops.nn.refresh_flipped``) after a pass
+        of its own over the updated weights (the pruning apply)."""
         lr = self.lr if lr is None else lr
         if self._dev is not None:
             self.set_dynamic(lr, grad_scale)
             self.launch(skip_flag)
-            from .nn import refresh_flipped
-            refresh_flipped()
+            if refresh:
+                from .nn import refresh_flipped
+                refresh_flipped()
         else:
             self._step_cpu(lr, grad_scale, skip_flag)
         self.num_updates += 1

@@ -18,7 +18,7 @@ import time
 import numpy as np
 import torch
 
-from .ckpt.saver import AdamPowerVar, Saver, TFVar, model_variables
+from .ckpt.saver import AdamPowerVar, MaskVar, Saver, TFVar, ThresholdVar, model_variables
 from .compat import logging
 from .compat.train import ExponentialDecay, LinearWarmup, PolynomialDecay, Server
 from .engine import TrainStep
@@ -124,6 +124,28 @@ DISTILL_BSP_ONLY = ("--distill_teacher needs --sync_mode bsp (got %s): under asp
                     "store's, which has no place for a second network's forward")
 
 
+PRUNE_BSP_ONLY = ("--prune_sparsity needs --sync_mode bsp (got %s): the masks agree between replicas without "
+                  "communication only because every rank holds the same weight bits, which asp / ssp do not give")
+
+
+def prune_config(FLAGS, mode):
+    """The PruneConfig of the --prune_* flags, or None with --prune_sparsity 0 (checked before any process group
+    exists).  --prune_exclude is a regular expression searched in a variable's TF name."""
+    if not FLAGS.prune_sparsity:
+        return None
+    if mode in ("asp", "ssp"):
+        raise ValueError(PRUNE_BSP_ONLY % mode)
+    import re
+    from .ops.prune import PruneConfig
+    select = None
+    if FLAGS.prune_exclude:
+        rx = re.compile(FLAGS.prune_exclude)
+        select = lambda name, p: p.dim() >= 2 and not rx.search(getattr(p, "tf_name", None) or name)  # noqa: E731
+    end = FLAGS.max_steps if FLAGS.prune_end_step < 0 else FLAGS.prune_end_step
+    return PruneConfig(FLAGS.prune_sparsity, FLAGS.prune_initial_sparsity, FLAGS.prune_begin_step, end,
+                       FLAGS.prune_frequency, FLAGS.prune_exponent, select)
+
+
 def parse_model_kw(text):
     """"k=v,..." -> {k: int or float}: the numeric model keywords of --distill_teacher_kw."""
     out = {}
@@ -214,6 +236,15 @@ def define_common_flags(flags, preset):
             ("distill_alpha", Fl, 0.5, "weight of the soft-target term, in [0, 1]"),
             ("distill_temperature", Fl, 4.0, "temperature of the soft targets"),
             # MI355X-native extras
+            # gradual magnitude pruning (ops.prune.PruneConfig; BSP only)
+            ("prune_sparsity", Fl, 0.0, "target sparsity of gradual magnitude pruning, in (0, 1) (0 = off)"),
+            ("prune_initial_sparsity", Fl, 0.0, "sparsity at --prune_begin_step"),
+            ("prune_begin_step", I, 0, "first step whose update re-selects the masks"),
+            ("prune_end_step", I, -1, "step at which the target is reached (-1 = --max_steps)"),
+            ("prune_frequency", I, 100, "steps between two mask updates"),
+            ("prune_exponent", Fl, 3.0, "exponent of the sparsity schedule"),
+            ("prune_exclude", S, "", "regular expression: variables whose TF name it matches stay dense (usually "
+             "the first conv and the logits)"),
             ("sync_mode", S, "", "bsp | asp | ssp (default from the entry script)"),
             ("max_staleness", I, 5, "SSP staleness bound in local steps"),
             ("synthetic_data", B, False, "use HBM-resident synthetic batches"),
@@ -329,6 +360,7 @@ def train(preset, flags, default_mode="bsp"):
         from .ops.mix import MixConfig
         mix_cfg = MixConfig(FLAGS.mixup_alpha, FLAGS.cutmix_alpha, FLAGS.mix_prob, FLAGS.mix_switch_prob,
                             FLAGS.mix_per_row, seed=FLAGS.seed)
+    prune_cfg = prune_config(FLAGS, mode)
     distill_ckpt = distill_kw = None
     if FLAGS.distill_teacher:
         if mode in ("asp", "ssp"):
@@ -455,20 +487,25 @@ def train(preset, flags, default_mode="bsp"):
                             else None, lars_eeta=FLAGS.lars_eeta, lars_epsilon=FLAGS.lars_epsilon,
                             clip_global_norm=FLAGS.clip_global_norm if FLAGS.clip_global_norm > 0 else None,
                             beta1=FLAGS.adam_beta1, beta2=FLAGS.adam_beta2, accum_steps=accum, mix=mix_cfg, rank=rank,
-                            distill=distill_cfg, **opt_kw)
-        vars_ = model_variables(model, step_fn.opt, gstep, **ckpt_kw)
+                            distill=distill_cfg, prune=prune_cfg, **opt_kw)
+        # (the pruner's <scope>/mask and <scope>/threshold in front of the global step, which stays last)
+        vars_ = model_variables(model, step_fn.opt, gstep, pruner=step_fn.pruner, **ckpt_kw)
         vars_[-1].name = cfg.get("global_step_name", "global_step")
         if path:
             Saver(vars_).restore(path)
         if world > 1:  # one collective replaces the reference's chief-init + 1 s polling of workers
             # (Adam's beta*_power scalars are host values derived from the step count, which every rank restores)
             pg.broadcast_tensors([v.tensor for v in vars_ if v.tensor.is_floating_point()
-                                  and not isinstance(v, AdamPowerVar)] + [b for b in model.buffers()])
+                                  and not isinstance(v, (AdamPowerVar, MaskVar, ThresholdVar))]
+                                 + [b for b in model.buffers()])
         from .ops.nn import invalidate_weight_copies
         invalidate_weight_copies(model.parameters())  # bf16 compute copies follow the restored weights
         step_fn.bufsync.resync()  # the BN statistics' sync snapshot follows the restored / broadcast values
         step_fn.global_step = int(gstep)
         step_fn.opt.restored(int(gstep))  # num_updates; Adam: the applied-update count from beta*_power
+        if step_fn.pruner is not None:
+            # every rank restored the same masks (all ones where the checkpoint held none): kept counts follow them
+            step_fn.pruner.masks_loaded()
     elif mode in ("asp", "ssp"):
         from .engine import moving_average_buffers, prepare_compute_copies
         from .parallel.asp import ASPTrainStep, ParamStore
@@ -620,6 +657,9 @@ def train(preset, flags, default_mode="bsp"):
                 extra["mix_lambda"] = step_fn.last_mix_lambda()  # mean own-label weight of this step (a host value)
             if distill_cfg is not None and metrics.f is not None:
                 extra["distill_kl"] = step_fn.last_distill_kl()  # a device read, after the synchronisation above
+            if prune_cfg is not None and metrics.f is not None:
+                # a device read, after the synchronisation above
+                extra["sparsity"], extra["prune_target"] = step_fn.last_sparsity()
             if metrics.f is not None and getattr(mkw.get("quantize"), "fused", False):
                 # device reads, after the logged step's synchronisation above
                 from .ops import fakequant

@@ -495,6 +495,217 @@ __global__ __launch_bounds__(256) void multi_tensor_adam_kernel(const OptTensor*
   }
 }
 
+// ---- LAMB (You et al. 2020: Adam's direction, decoupled weight decay, LARS's per-tensor trust ratio) --------------
+//   m = b1*m + (1-b1)*gs;  v = b2*v + (1-b2)*gs*gs;  r = (m/bc1) / (sqrt(v)/bc2 + eps) + wd_t*p     (gs = g*grad_scale)
+//   phi[t] = |p| / |r|  if tensor t is adapted, |p| > 0 and |r| > 0, else 1;   p -= (lr*lr_mult[t]*phi[t]) * r
+// |r| needs the moments AFTER they took this step's gradient, so the pass has launches of its own over the Adam
+// tables (s1 = m, s2 = v, the AdamState record) and the norm pass's side table and scratch:
+//   launch 1: adam_advance_kernel;
+//   launch 2: one block per OptChunk row: m, v updated and stored, one record {sum p^2, sum gs^2, sum r^2} (fp64, the
+//             norm pass's fixed order) per row;
+//   launch 3: one block, one wave per tensor: norms[t] = {|p|, |r|, |gs|}, lr_scale[t] = phi[t];
+//   launch 4: one block per OptChunk row: r again from the stored p, m, v (p has not changed in between, so these
+//             are the bits launch 2 reduced), then p, its bf16 copy and the EMA shadow.
+// No float atomics, flags or inter-block waiting; every launch leaves at once on the skip flag.
+struct LambHyper {
+  float b1, omb1, b2, omb2, eps;
+  int use_ema;
+  const int* skip_flag;
+  const float* dyn;  // device scalars [lr, ema_decay, grad_scale]
+  const AdamState* state;
+  const float* lr_scale;  // phi per tensor (launch 4)
+};
+
+// One element, every operation spelled out (as adam_elem): launches 2 and 4 and both access paths of each form r
+// here, from the same p, m, v.
+__device__ __forceinline__ float lamb_gs(float graw, float grad_scale) { return __fmul_rn(graw, grad_scale); }
+__device__ __forceinline__ void lamb_moments(float g, float& m, float& v, const LambHyper& h) {
+  m = __fmaf_rn(h.b1, m, __fmul_rn(h.omb1, g));
+  v = __fmaf_rn(h.b2, v, __fmul_rn(__fmul_rn(h.omb2, g), g));
+}
+// (sqrtf, not __fsqrt_rn: the intrinsic is the native root, good to 1 ulp, while sqrtf is correctly rounded like the
+// quotients - so a host evaluation with IEEE fp32 operations reproduces r)
+__device__ __forceinline__ float lamb_dir(float p, float m, float v, float wd, float bc1, float bc2, float eps) {
+  return __fmaf_rn(wd, p, __fdiv_rn(__fdiv_rn(m, bc1), __fadd_rn(__fdiv_rn(sqrtf(v), bc2), eps)));
+}
+// (NormRec::ge2 carries sum r^2 here: r takes the place of the effective gradient)
+__device__ __forceinline__ void lamb_acc(NormRec& a, float p, float gs, float r) {
+  a.p2 += (double)p * (double)p;
+  a.gs2 += (double)gs * (double)gs;
+  a.ge2 += (double)r * (double)r;
+}
+
+// 16 B read + 8 B written per element: 16-byte accesses where weight, gradient, m and v reach a 16-byte boundary
+// together, with a scalar head and tail; coalesced 4-byte accesses otherwise.
+__global__ __launch_bounds__(256) void multi_tensor_lamb_moments_kernel(const OptTensor* __restrict__ tens,
+                                                                        const OptChunk* __restrict__ chunks,
+                                                                        LambHyper h, NormRec* __restrict__ recs) {
+  if (h.skip_flag && *h.skip_flag) return;  // m, v and the records stay
+  __shared__ double red[4][3];
+  const int tid = threadIdx.x;
+  const OptChunk c = chunks[blockIdx.x];
+  const OptTensor t = tens[c.t];
+  NormRec a = {0.0, 0.0, 0.0};
+  if (t.g) {  // (an EMA-only row writes a zero record)
+    const long rem = t.n - c.start;
+    const int len = (int)(rem < (long)OPT_CHUNK ? (rem > 0 ? rem : 0) : (long)OPT_CHUNK);
+    const float grad_scale = h.dyn[2];
+    const AdamState s = *h.state;
+    const float* pp = t.p + c.start;
+    const float* gp = t.g + c.start;
+    float* mp = t.s1 + c.start;
+    float* vp = t.s2 + c.start;
+
+    auto scalar = [&](int i) {
+      const float p = pp[i], g = lamb_gs(gp[i], grad_scale);
+      float m = mp[i], v = vp[i];
+      lamb_moments(g, m, v, h);
+      mp[i] = m; vp[i] = v;
+      lamb_acc(a, p, g, lamb_dir(p, m, v, t.wd, s.bc1, s.bc2, h.eps));
+    };
+
+    const uintptr_t pa = (uintptr_t)pp;
+    const uintptr_t off = (pa ^ (uintptr_t)gp) | (pa ^ (uintptr_t)mp) | (pa ^ (uintptr_t)vp);
+    if ((off & 15u) == 0) {
+      int head = (int)(((16u - (unsigned)(pa & 15u)) & 15u) >> 2);  // elements up to the 16-byte boundary
+      head = head < len ? head : len;
+      const int nvec = (len - head) >> 2, tail0 = head + (nvec << 2);
+      if (tid < head) scalar(tid);
+      const f32x4* pv = (const f32x4*)(pp + head);
+      const f32x4* gv = (const f32x4*)(gp + head);
+      f32x4* mv = (f32x4*)(mp + head);
+      f32x4* vv = (f32x4*)(vp + head);
+      for (int i = tid; i < nvec; i += 256) {
+        const f32x4 pw = pv[i], gw = gv[i];
+        f32x4 mw = mv[i], vw = vv[i];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float g = lamb_gs(gw[e], grad_scale);
+          float m = mw[e], v = vw[e];
+          lamb_moments(g, m, v, h);
+          mw[e] = m; vw[e] = v;
+          lamb_acc(a, pw[e], g, lamb_dir(pw[e], m, v, t.wd, s.bc1, s.bc2, h.eps));
+        }
+        mv[i] = mw; vv[i] = vw;
+      }
+      if (tail0 + tid < len) scalar(tail0 + tid);
+    } else {
+      for (int i = tid; i < len; i += 256) scalar(i);
+    }
+  }
+  // fixed order: xor butterfly over each wave, then the four waves in LDS (as multi_tensor_norm_kernel)
+  a.p2 = wave_sum_f64(a.p2);
+  a.gs2 = wave_sum_f64(a.gs2);
+  a.ge2 = wave_sum_f64(a.ge2);
+  if ((tid & 63) == 0) {
+    red[tid >> 6][0] = a.p2; red[tid >> 6][1] = a.gs2; red[tid >> 6][2] = a.ge2;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    NormRec r;
+    r.p2 = (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]);
+    r.gs2 = (red[0][1] + red[1][1]) + (red[2][1] + red[3][1]);
+    r.ge2 = (red[0][2] + red[1][2]) + (red[2][2] + red[3][2]);
+    recs[blockIdx.x] = r;
+  }
+}
+
+__global__ __launch_bounds__(NORM_FIN_THREADS) void multi_tensor_lamb_finalize_kernel(
+    const NormMeta* __restrict__ meta, int ntens, const NormRec* __restrict__ recs, const int* skip_flag,
+    float* __restrict__ norms, float* __restrict__ lr_scale) {
+  if (skip_flag && *skip_flag) return;  // the previous step's outputs stay
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  for (int t = wv; t < ntens; t += NORM_FIN_THREADS / 64) {  // one wave per tensor
+    const NormMeta m = meta[t];
+    double p2 = 0.0, gs2 = 0.0, r2 = 0.0;
+    for (int j = lane; j < m.nchunks; j += 64) {
+      const NormRec r = recs[m.chunk0 + j];
+      p2 += r.p2; gs2 += r.gs2; r2 += r.ge2;
+    }
+    p2 = wave_sum_f64(p2);
+    gs2 = wave_sum_f64(gs2);
+    r2 = wave_sum_f64(r2);
+    if (lane == 0) {
+      const double pn = sqrt(p2), rn = sqrt(r2);
+      norms[3 * t] = (float)pn;
+      norms[3 * t + 1] = (float)rn;
+      norms[3 * t + 2] = (float)sqrt(gs2);
+      lr_scale[t] = (m.adapt && pn > 0.0 && rn > 0.0) ? (float)(pn / rn) : 1.f;  // (a NaN norm fails both tests)
+    }
+  }
+}
+
+// 12 B read + 6 B written per element with the bf16 copy (+8 B EMA): 16-byte accesses where weight, m, v (and the
+// shadow; the bf16 copy at 8 bytes) reach a 16-byte boundary together, as multi_tensor_adam_kernel chooses.
+__global__ __launch_bounds__(256) void multi_tensor_lamb_apply_kernel(const OptTensor* __restrict__ tens,
+                                                                      const OptChunk* __restrict__ chunks,
+                                                                      LambHyper h) {
+  if (h.skip_flag && *h.skip_flag) return;
+  const int tid = threadIdx.x;
+  const OptChunk c = chunks[blockIdx.x];
+  const OptTensor t = tens[c.t];
+  const long rem = t.n - c.start;
+  const int len = (int)(rem < (long)OPT_CHUNK ? (rem > 0 ? rem : 0) : (long)OPT_CHUNK);
+  const float ema_decay = h.dyn[1];
+  if (!t.g) {  // EMA-only row (BN moving statistics), as in multi_tensor_opt_kernel
+    if (h.use_ema && t.ema) {
+      const float* bp = t.p + c.start;
+      float* sp = t.ema + c.start;
+      for (int i = tid; i < len; i += 256) sp[i] -= (1.f - ema_decay) * (sp[i] - bp[i]);
+    }
+    return;
+  }
+  const AdamState s = *h.state;
+  const float step = __fmul_rn(__fmul_rn(h.dyn[0], t.lr_mult), h.lr_scale[c.t]);
+  const float omd = 1.f - ema_decay;
+  float* pp = t.p + c.start;
+  const float* mp = t.s1 + c.start;
+  const float* vp = t.s2 + c.start;
+  float* ep = (h.use_ema && t.ema) ? t.ema + c.start : nullptr;
+  bf16_t* cp = t.pcopy ? t.pcopy + c.start : nullptr;
+
+  auto elem = [&](float p, float m, float v) {
+    return __fmaf_rn(-step, lamb_dir(p, m, v, t.wd, s.bc1, s.bc2, h.eps), p);
+  };
+  auto scalar = [&](int i) {
+    const float p = elem(pp[i], mp[i], vp[i]);
+    pp[i] = p;
+    if (cp) cp[i] = f2bf(p);
+    if (ep) ep[i] = ema_elem(ep[i], p, omd);
+  };
+
+  const uintptr_t pa = (uintptr_t)pp;
+  uintptr_t off = (pa ^ (uintptr_t)mp) | (pa ^ (uintptr_t)vp);
+  if (ep) off |= pa ^ (uintptr_t)ep;
+  const int head16 = (int)(((16u - (unsigned)(pa & 15u)) & 15u) >> 2);  // elements up to the 16-byte boundary
+  if ((off & 15u) == 0 && (!cp || ((uintptr_t)(cp + head16) & 7u) == 0)) {
+    const int head = head16 < len ? head16 : len;
+    const int nvec = (len - head) >> 2, tail0 = head + (nvec << 2);
+    if (tid < head) scalar(tid);
+    f32x4* pv = (f32x4*)(pp + head);
+    const f32x4* mv = (const f32x4*)(mp + head);
+    const f32x4* vv = (const f32x4*)(vp + head);
+    for (int i = tid; i < nvec; i += 256) {
+      f32x4 pw = pv[i];
+      const f32x4 mw = mv[i], vw = vv[i];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) pw[e] = elem(pw[e], mw[e], vw[e]);
+      pv[i] = pw;
+      if (cp) ((uint2*)(cp + head))[i] = make_uint2(pack2bf(pw[0], pw[1]), pack2bf(pw[2], pw[3]));
+      if (ep) {
+        f32x4* ev = (f32x4*)(ep + head);
+        f32x4 ew = ev[i];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) ew[e] = ema_elem(ew[e], pw[e], omd);
+        ev[i] = ew;
+      }
+    }
+    if (tail0 + tid < len) scalar(tail0 + tid);
+  } else {
+    for (int i = tid; i < len; i += 256) scalar(i);
+  }
+}
+
 __global__ void check_finite_kernel(const float* __restrict__ x, long n, int* __restrict__ flag) {
   bool bad = false;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
@@ -712,6 +923,39 @@ DTM_API int dtm_multi_tensor_norms(const void* tensors_dev, const void* chunks_d
   hipLaunchKernelGGL(multi_tensor_norm_finalize_kernel, dim3(1), dim3(NORM_FIN_THREADS), 0, (hipStream_t)stream,
                      (const OptTensor*)tensors_dev, (const NormMeta*)meta_dev, ntens, (const NormRec*)recs, h, tsum,
                      norms, lr_scale, gclip);
+  return 0;
+}
+
+// The LAMB step over the optimizer's tables (s1 = m, s2 = v; meta_dev / scratch / norms / lr_scale as
+// dtm_multi_tensor_norms, state / dyn as dtm_multi_tensor_adam): four launches in stream order - the state advance,
+// the moments pass with the per-row records, the per-tensor finalize (norms [ntens][3] = {|p|, |r|, |gs|}, lr_scale
+// [ntens] = phi) and the apply pass.  Nothing is allocated, uploaded or read back, so the step can be captured into a
+// hipGraph.  Returns -1 for a bad count or a null table, -2 for a beta outside [0, 1) or eps < 0 (NaN included);
+// nothing is launched then.
+DTM_API int dtm_multi_tensor_lamb(const void* tensors_dev, const void* chunks_dev, int num_chunks,
+                                  const void* meta_dev, int ntens, double b1, double b2, double eps, int use_ema,
+                                  const int* skip_flag, const float* dyn, void* state, void* scratch, float* norms,
+                                  float* lr_scale, void* stream) {
+  if (num_chunks < 0 || ntens < 0 || !dyn || !state) return -1;
+  if (ntens > 0 && (!tensors_dev || !meta_dev || !scratch || !norms || !lr_scale)) return -1;
+  if (num_chunks > 0 && (!chunks_dev || ntens == 0)) return -1;
+  if (!(b1 >= 0.0 && b1 < 1.0) || !(b2 >= 0.0 && b2 < 1.0) || !(eps >= 0.0)) return -2;
+  LambHyper h;
+  h.b1 = (float)b1; h.omb1 = (float)(1.0 - b1); h.b2 = (float)b2; h.omb2 = (float)(1.0 - b2); h.eps = (float)eps;
+  h.use_ema = use_ema; h.skip_flag = skip_flag; h.dyn = dyn; h.state = (const AdamState*)state;
+  h.lr_scale = lr_scale;
+  NormRec* recs = (NormRec*)scratch;
+  hipLaunchKernelGGL(adam_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (AdamState*)state, skip_flag, b1,
+                     b2);
+  if (num_chunks > 0)
+    hipLaunchKernelGGL(multi_tensor_lamb_moments_kernel, dim3(num_chunks), dim3(256), 0, (hipStream_t)stream,
+                       (const OptTensor*)tensors_dev, (const OptChunk*)chunks_dev, h, recs);
+  if (ntens > 0)
+    hipLaunchKernelGGL(multi_tensor_lamb_finalize_kernel, dim3(1), dim3(NORM_FIN_THREADS), 0, (hipStream_t)stream,
+                       (const NormMeta*)meta_dev, ntens, (const NormRec*)recs, skip_flag, norms, lr_scale);
+  if (num_chunks > 0)
+    hipLaunchKernelGGL(multi_tensor_lamb_apply_kernel, dim3(num_chunks), dim3(256), 0, (hipStream_t)stream,
+                       (const OptTensor*)tensors_dev, (const OptChunk*)chunks_dev, h);
   return 0;
 }
 

@@ -8,7 +8,8 @@
   of TensorFlow's own contrib LARS optimizer is not checked here, TensorFlow is not part of the test environment),
   ``<v>/RMSProp``, ``<v>/RMSProp_1``; Adam ``<v>/Adam`` (m), ``<v>/Adam_1`` (v) and the scalars ``beta1_power``,
   ``beta2_power`` = b^(t+1) after t applied updates, from which a restore recovers t (parity of these names with a
-  file written by TensorFlow itself is not checked either); EMA shadows
+  file written by TensorFlow itself is not checked either; LAMB writes the same four names, so Adam and LAMB runs
+  resume into each other); EMA shadows
   ``<v>/ExponentialMovingAverage``; ``global_step`` int64; for a pruned ``<scope>/weights`` (ops/prune.py)
   ``<scope>/mask`` (float32, the weight's shape and layout) and ``<scope>/threshold`` (a float32 scalar holding the
   bit pattern of the threshold key), optional on restore (parity of these names with a file written by
@@ -156,7 +157,7 @@ def model_variables(model, optimizer=None, global_step=None, include_slots=True,
             elif optimizer.kind == "rmsprop":
                 out.append(TFVar(base.name + "/RMSProp", st["s2"], base.layout, partitions))
                 out.append(TFVar(base.name + "/RMSProp_1", st["s1"], base.layout, partitions))
-            elif optimizer.kind == "adam":
+            elif optimizer.kind in ("adam", "lamb"):  # LAMB keeps Adam's slots and their names
                 out.append(TFVar(base.name + "/Adam", st["s1"], base.layout, partitions))
                 out.append(TFVar(base.name + "/Adam_1", st["s2"], base.layout, partitions))
             if "ema" in st:
@@ -165,7 +166,7 @@ def model_variables(model, optimizer=None, global_step=None, include_slots=True,
             base = by_param.get(id(b))
             if base is not None:
                 out.append(TFVar(base.name + "/ExponentialMovingAverage", shadow, base.layout, partitions))
-        if optimizer.kind == "adam":
+        if optimizer.kind in ("adam", "lamb"):
             out.append(AdamPowerVar(prefix + "beta1_power", optimizer, 0))
             out.append(AdamPowerVar(prefix + "beta2_power", optimizer, 1))
     if pruner is not None:

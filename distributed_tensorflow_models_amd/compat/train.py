@@ -252,6 +252,18 @@ class AdamOptimizer(Optimizer):
         super().__init__(learning_rate, beta1=beta1, beta2=beta2, epsilon=epsilon)
 
 
+class LAMBOptimizer(Optimizer):
+    """LAMB (You et al. 2020; ops/optim.py): Adam's direction with decoupled weight decay, scaled per variable by the
+    trust ratio |w| / |r|; variables of rank <= 1 (biases, BN beta / gamma) keep lr.  ``weight_decay``: the
+    coefficient of every trainable variable, as LARSOptimizer's (None: each variable keeps its own ``weight_decay``
+    attribute) - used decoupled by this optimizer.  BSP / single-worker only."""
+    kind = "lamb"
+
+    def __init__(self, learning_rate=0.001, beta1=0.9, beta2=0.999, epsilon=1e-6, weight_decay=None):
+        super().__init__(learning_rate, beta1=beta1, beta2=beta2, epsilon=epsilon)
+        self.weight_decay = weight_decay
+
+
 class SyncReplicasOptimizer:
     """BSP wrapper: gradients of all replicas are averaged before one update (C9).  With
     replicas_to_aggregate == total_num_replicas (every reference call site) this is exactly a
@@ -458,9 +470,10 @@ class TrainOp:
             raise ValueError("LARSOptimizer and clip_global_norm need the BSP step (SyncReplicasOptimizer or one "
                              "worker): under ASP the update runs on owner shards from one worker's push, where no "
                              "global gradient norm exists")
-        if base.kind == "adam" and self.mode != "bsp":
-            raise ValueError("AdamOptimizer needs the BSP step (SyncReplicasOptimizer or one worker): the owner "
-                             "shards of ASP keep no shared count of applied updates for the bias correction")
+        if base.kind in ("adam", "lamb") and self.mode != "bsp":
+            raise ValueError("%s needs the BSP step (SyncReplicasOptimizer or one worker): the owner "
+                             "shards of ASP keep no shared count of applied updates for the bias correction"
+                             % type(base).__name__)
         if weight_decay is None:
             weight_decay = getattr(base, "weight_decay", None)
         if weight_decay is not None:

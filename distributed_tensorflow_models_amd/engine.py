@@ -139,8 +139,9 @@ class TrainStep:
                  grad_comm_dtype=None, ema_buffers=True, bn_sync_every=1, wgrad_stream=None, bsp_check=None,
                  overlap=True, force_comm=False, graph_comm=False, lars_eeta=0.001, lars_epsilon=0.0,
                  clip_global_norm=None, beta1=0.9, beta2=0.999, accum_steps=1, mix=None, rank=None,
-                 distill=None, prune=None):
-        # epsilon None: the optimizer's own default (1e-10; Adam 1e-8); beta1 / beta2: Adam only
+                 distill=None, prune=None, lars_skip=None):
+        # epsilon None: the optimizer's own default (1e-10; Adam 1e-8; LAMB 1e-6); beta1 / beta2: Adam and LAMB
+        # lars_skip: predicate on a parameter, True = no trust ratio for it under lars / lamb (default: ndim <= 1)
         # accum_steps N: a call runs N micro-batches, sums their gradients (parallel/bsp.py begin_micro /
         # accumulate) and applies ONE update: an effective batch of N times the micro-batch on the same memory
         # mix: an ops.mix.MixConfig - every micro-batch is mixed with a permutation of itself (mixup / CutMix) into
@@ -213,7 +214,7 @@ class TrainStep:
                                   ema_buffers=moving_average_buffers(model)
                                   if (ema_decay is not None and ema_buffers) else (),
                                   lars_eeta=lars_eeta, lars_epsilon=lars_epsilon, clip_global_norm=clip_global_norm,
-                                  beta1=beta1, beta2=beta2)
+                                  beta1=beta1, beta2=beta2, lars_skip=lars_skip)
         if prune is not None:
             pruned = [(name, p) for name, p in model.named_parameters() if p.requires_grad and prune.selects(name, p)]
             self.pruner = _prune.Pruner([(name, p.data, getattr(p, "bf16", None), self.opt.state[p].get("ema"))

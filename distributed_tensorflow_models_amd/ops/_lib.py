@@ -115,6 +115,7 @@ _SIGS = {
     "dtm_multi_tensor_norms": (_I, [_P, _P, _I, _P, _I, _P, _F, _F, _F, _F, _P, _P, _P, _P, _P]),
     "dtm_adam_state_bytes": (_I, []),
     "dtm_multi_tensor_adam": (_I, [_P, _P, _I, _D, _D, _D, _I, _P, _P, _P, _P, _P]),
+    "dtm_multi_tensor_lamb": (_I, [_P, _P, _I, _P, _I, _D, _D, _D, _I, _P, _P, _P, _P, _P, _P, _P]),
     "dtm_check_finite": (None, [_P, _L, _P, _P]),
     "dtm_grad_accum": (_I, [_P, _P, _L, _I, _P, _P]),
     "dtm_prune_tensor_bytes": (_I, []),

@@ -17,14 +17,25 @@ TF 1.x update semantics:
                             guard skips on the device does not count, so t lives in a small device record that a
                             one-thread launch advances in front of the update (also inside a replayed hipGraph); the
                             host reads it only in ``adam_step()``.  Weight decay stays the coupled L2 term (no AdamW).
-  g = grad*grad_scale + weight_decay*p   (coupled L2 = d/dp of wd*sum(p^2)/2; K14)
+  LAMB (You et al. 2020)    gs = grad*grad_scale;  m = b1*m + (1-b1)*gs;  v = b2*v + (1-b2)*gs*gs;
+                            r = (m / (1-b1^t)) / (sqrt(v) / sqrt(1-b2^t) + eps) + wd_t*p;
+                            phi[t] = |p| / |r| for an adapted tensor with |p| > 0 and |r| > 0, 1 otherwise (no clamp);
+                            p -= lr*lr_mult[t]*phi[t] * r
+                            (eps outside the root, added to the bias-corrected sqrt(v): the paper's and TensorFlow
+                            Addons' form; t and the slots are Adam's).  The weight decay is DECOUPLED for this kind:
+                            wd_t*p enters r only, never gs, m or v - the same ``weight_decay`` number that is the
+                            coupled L2 term under every other kind.  |r| depends on the moments after this step's
+                            gradient, so the kind has a pass of its own: state advance, moments + per-chunk fp64
+                            records, per-tensor finalize, apply (four launches, no host decision in between).
+  g = grad*grad_scale + weight_decay*p   (coupled L2 = d/dp of wd*sum(p^2)/2; K14; every kind but LAMB)
   clip_global_norm (tf.clip_by_global_norm): g *= clip / max(sqrt(sum over all tensors of |g|^2), clip); the L2
                             term is part of g because the reference puts it in the loss
   optional ExponentialMovingAverage shadows: ema -= (1-d)(ema - p), d = min(decay,(1+n)/(10+n)) (C22)
 and a bf16 copy-out of every updated weight (the compute copy read by the conv kernels).
 
 The norms LARS and clipping need come from one two-launch multi-tensor pass on the device (fp64 sums in a fixed
-order: bit-identical on every rank), enqueued before the update; the host never waits for them.
+order: bit-identical on every rank), enqueued before the update; the host never waits for them.  LAMB's norms (|p|,
+|r|, |gs|) come out of its own pass in the same fixed order.
 
 On CPU the same math runs as torch ops (gloo plumbing tests, reference checks).
 """
@@ -36,8 +47,10 @@ import torch
 
 from . import _lib
 
-# kernel update rule per kind (LARS is the momentum rule with a per-tensor rate factor; Adam has its own entry point)
-KINDS = {"sgd": 0, "momentum": 1, "rmsprop": 2, "lars": 1, "adam": 3}
+# kernel update rule per kind (LARS is the momentum rule with a per-tensor rate factor; Adam and LAMB have entry
+# points of their own)
+KINDS = {"sgd": 0, "momentum": 1, "rmsprop": 2, "lars": 1, "adam": 3, "lamb": 4}
+ADAM_LIKE = ("adam", "lamb")  # m, v slots at the weight's offset and the device record of applied updates
 
 
 def _bias_corrections(b1, b2, t):
@@ -60,9 +73,12 @@ class FusedOptimizer:
     def __init__(self, params, kind="momentum", lr=0.1, momentum=0.9, rho=0.9, epsilon=None, ema_decay=None,
                  weight_decay=None, lr_mults=None, ema_buffers=(), lars_eeta=0.001, lars_epsilon=0.0,
                  clip_global_norm=None, lars_skip=None, beta1=0.9, beta2=0.999):
-        """``lars_skip``: predicate on a parameter, True = its rate is not adapted (default: ``p.ndim <= 1``).
-        ``clip_global_norm``: threshold of the clip by global norm (None or 0: off); not combined with LARS.
-        ``epsilon``: None = 1e-10 (RMSProp's) or, for Adam, 1e-8.  ``beta1`` / ``beta2``: Adam only."""
+        """``lars_skip``: predicate on a parameter, True = its rate is not adapted (default: ``p.ndim <= 1``); it
+        serves LARS and LAMB alike.  ``kind="lamb"`` with a predicate that skips every tensor is AdamW (decoupled
+        decay, no trust ratio).
+        ``clip_global_norm``: threshold of the clip by global norm (None or 0: off); not combined with LARS or LAMB.
+        ``epsilon``: None = 1e-10 (RMSProp's), for Adam 1e-8, for LAMB 1e-6.  ``beta1`` / ``beta2``: Adam and LAMB.
+        ``weight_decay`` (or ``p.weight_decay``): the coupled L2 term, except under LAMB, where it is decoupled."""
         self.params = [p for p in params if p.requires_grad]
         # non-trainable tensors that also get an EMA shadow (BN moving mean/variance: the reference
         # averages trainable_variables() + moving_average_variables(), e.g. reference
@@ -76,14 +92,20 @@ class FusedOptimizer:
             raise ValueError("clip_global_norm must be positive, got %r" % (clip_global_norm,))
         if kind == "lars" and clip > 0.0:
             raise ValueError("LARS and clip_global_norm are not combined (the order of the two is not defined)")
+        if kind == "lamb" and clip > 0.0:
+            raise ValueError("LAMB and clip_global_norm are not combined (the global norm would have to leave the "
+                             "decoupled decay term out, which the norm pass does not form)")
         if epsilon is None:
-            epsilon = 1e-8 if kind == "adam" else 1e-10
+            epsilon = {"adam": 1e-8, "lamb": 1e-6}.get(kind, 1e-10)
         self.kind, self.lr, self.mu, self.rho, self.eps = kind, lr, momentum, rho, epsilon
         self.b1, self.b2 = float(beta1), float(beta2)
-        if kind == "adam" and not (0.0 <= self.b1 < 1.0 and 0.0 <= self.b2 < 1.0):
+        if kind in ADAM_LIKE and not (0.0 <= self.b1 < 1.0 and 0.0 <= self.b2 < 1.0):
             raise ValueError("beta1 and beta2 must be in [0, 1), got %r, %r" % (beta1, beta2))
+        if kind == "lamb" and not float(epsilon) >= 0.0:
+            raise ValueError("epsilon must not be negative, got %r" % (epsilon,))
         self.lars_eeta, self.lars_eps, self.clip = float(lars_eeta), float(lars_epsilon), clip
         self.scaled = kind == "lars" or clip > 0.0  # the step needs the norm pass
+        self.normed = self.scaled or kind == "lamb"  # ... or writes norms and rate factors itself
         if lars_skip is None:
             lars_skip = lambda p: p.ndim <= 1  # noqa: E731
         self.ema_decay = ema_decay
@@ -95,20 +117,20 @@ class FusedOptimizer:
                 st["s1"] = torch.zeros_like(p, dtype=torch.float32)
             if kind == "rmsprop":
                 st["s2"] = torch.ones_like(p, dtype=torch.float32)  # TF RMSProp ms slot init 1.0
-            if kind == "adam":
+            if kind in ADAM_LIKE:
                 st["s1"], st["s2"] = _slot_like(p), _slot_like(p)  # m, v
             if ema_decay is not None:
-                st["ema"] = _slot_like(p).copy_(p.detach()) if kind == "adam" else p.detach().clone().float()
+                st["ema"] = _slot_like(p).copy_(p.detach()) if kind in ADAM_LIKE else p.detach().clone().float()
             st["wd"] = float(getattr(p, "weight_decay", 0.0) if weight_decay is None else weight_decay)
             st["lr_mult"] = 1.0 if lr_mults is None else float(lr_mults.get(p, 1.0))
-            st["adapt"] = kind == "lars" and not lars_skip(p)
+            st["adapt"] = kind in ("lars", "lamb") and not lars_skip(p)
             self.state[p] = st
         self._dev = None
         self._norms = self._lr_scale = self._gclip = None
         self._adam_t = 0          # CPU path: applied updates (the device path keeps them in _adam_state)
         self._adam_state = None   # device record {int32 t, fp32 1-b1^t, fp32 sqrt(1-b2^t), pad}
         self._adam_loaded = {}    # beta*_power values a checkpoint restore delivered (restored())
-        if self.scaled and not (self.params and self.params[0].is_cuda):
+        if self.normed and not (self.params and self.params[0].is_cuda):
             n = len(self.params) + len(self.ema_buffers)
             self._norms = torch.zeros((n, 3), dtype=torch.float32)
             self._lr_scale = torch.ones(n, dtype=torch.float32)
@@ -157,7 +179,7 @@ class FusedOptimizer:
         self._tens_dev = torch.from_numpy(tens.view(np.uint8).reshape(-1).copy()).to(dev)
         self._chunks_dev = torch.from_numpy(ct.view(np.uint8).reshape(-1).copy()).to(dev)
         self._nchunks = len(chunks)
-        if self.scaled:
+        if self.normed:
             # the norm pass: a side table beside the 64-byte tensor rows (first chunk row, row count, LARS flag),
             # its scratch (one fp64 record per chunk row) and its outputs - all allocated here, none in launch()
             ntens = tens.shape[0]
@@ -177,7 +199,7 @@ class FusedOptimizer:
             self._norms = torch.zeros((ntens, 3), dtype=torch.float32, device=dev)
             self._lr_scale = torch.ones(ntens, dtype=torch.float32, device=dev)
             self._gclip = torch.ones(1, dtype=torch.float32, device=dev)
-        if self.kind == "adam":
+        if self.kind in ADAM_LIKE:
             assert L.dtm_adam_state_bytes() == 16
             self._adam_state = torch.zeros(4, dtype=torch.int32, device=dev)
         self._dyn = torch.zeros(3, dtype=torch.float32, device=dev)
@@ -221,6 +243,16 @@ class FusedOptimizer:
     def launch(self, skip_flag=None):
         """Issue the fused update reading lr/ema/grad_scale from the device scalars."""
         L = _lib.lib()
+        if self.kind == "lamb":
+            # state advance, moments + records, finalize (norms, trust ratios), apply: all inside the entry point
+            rc = L.dtm_multi_tensor_lamb(_lib.ptr(self._tens_dev), _lib.ptr(self._chunks_dev), self._nchunks,
+                                         _lib.ptr(self._meta_dev), self._ntens, self.b1, self.b2, float(self.eps),
+                                         int(self.ema_decay is not None), _lib.ptr(skip_flag), _lib.ptr(self._dyn),
+                                         _lib.ptr(self._adam_state), _lib.ptr(self._norm_scratch),
+                                         _lib.ptr(self._norms), _lib.ptr(self._lr_scale), _lib.stream_ptr())
+            if rc != 0:
+                raise RuntimeError("dtm_multi_tensor_lamb failed (%d)" % rc)
+            return
         if self.kind == "adam":
             # norm pass when clipping, then the state advance and the update (both inside the entry point)
             if self.scaled:
@@ -261,12 +293,15 @@ class FusedOptimizer:
     def last_norms(self):
         """The device tensor [ntens, 3] of (|p|, |grad*grad_scale|, |grad*grad_scale + wd*p|) per table row (the
         parameters in order, then the EMA-only rows, which stay 0) that the last step's norm pass wrote; None when
-        neither LARS nor clipping is on.  Returned without synchronising: the global gradient norm is
-        ``last_norms()[:, 2].double().square().sum().sqrt()``, the trust ratios are ``last_lr_scale()``."""
+        none of LARS, clipping and LAMB is on.  Returned without synchronising: the global gradient norm is
+        ``last_norms()[:, 2].double().square().sum().sqrt()``, the trust ratios are ``last_lr_scale()``.
+        Under LAMB the columns are (|p|, |r|, |grad*grad_scale|) of the last applied step, r being the update
+        direction with its decoupled decay term."""
         return self._norms
 
     def last_lr_scale(self):
-        """The device tensor [ntens] of per-tensor rate factors (LARS trust ratios; 1 where not adapted)."""
+        """The device tensor [ntens] of per-tensor rate factors (LARS trust ratios, LAMB's phi; 1 where not
+        adapted)."""
         return self._lr_scale
 
     def norm_stats(self):
@@ -274,16 +309,18 @@ class FusedOptimizer:
         if self._norms is None:
             return {}
         n = self._norms.detach().cpu().double()
-        out = {"grad_norm": float(n[:, 2].square().sum().sqrt())}
+        out = {"grad_norm": float(n[:, 2].square().sum().sqrt())}  # (LAMB: |gs|, no decay term in it)
+        if self.kind == "lamb":
+            out["update_norm"] = float(n[:, 1].square().sum().sqrt())
         adapted = [i for i, p in enumerate(self.params) if self.state[p]["adapt"]]
-        if self.kind == "lars" and adapted:
+        if self.kind in ("lars", "lamb") and adapted:
             r = self._lr_scale.detach().cpu()[adapted]
-            out["lars/min_trust_ratio"], out["lars/max_trust_ratio"] = float(r.min()), float(r.max())
+            out[self.kind + "/min_trust_ratio"], out[self.kind + "/max_trust_ratio"] = float(r.min()), float(r.max())
         return out
 
     def adam_step(self):
-        """The number of Adam updates applied so far (skipped ones not counted).  Reads the device: call it on
-        logged steps and at checkpoints only."""
+        """The number of Adam (or LAMB) updates applied so far (skipped ones not counted).  Reads the device: call it
+        on logged steps and at checkpoints only."""
         if self._adam_state is not None:
             return int(self._adam_state[0].item())
         return self._adam_t
@@ -310,7 +347,7 @@ class FusedOptimizer:
         recovered from the restored beta2_power (b2^(t+1)), from beta1_power when b2 is 0 or the entry was absent
         (or has underflowed), and from ``global_step`` when neither is there."""
         self.num_updates = int(global_step)
-        if self.kind != "adam":
+        if self.kind not in ADAM_LIKE:
             return
         t = None
         for name, b in (("beta2_power", self.b2), ("beta1_power", self.b1)):
@@ -341,7 +378,7 @@ class FusedOptimizer:
             return
         d = self.ema_decay_now()
         gclip = 1.0
-        if self.kind == "adam":  # applied updates only: the early return above leaves the count alone
+        if self.kind in ADAM_LIKE:  # applied updates only: the early return above leaves the count alone
             self._adam_t += 1
             bc1, bc2 = _bias_corrections(self.b1, self.b2, self._adam_t)
         if self.scaled:  # the norm pass: fp32 terms as the kernel forms them, fp64 sums
@@ -367,12 +404,32 @@ class FusedOptimizer:
             if self.clip > 0.0:
                 gclip = float(np.float32(self.clip / max(math.sqrt(total), self.clip)))
             self._gclip.fill_(gclip)
+        if self.kind == "lamb":
+            self._norms.zero_()
+            self._lr_scale.fill_(1.0)
         for i, p in enumerate(self.params):
             st = self.state[p]
             g = getattr(p, "main_grad", None)
             if g is None:
                 g = p.grad
             if g is None:
+                continue
+            if self.kind == "lamb":  # fp32 terms, fp64 sums, phi and the step rounded to fp32 as in the kernels
+                gs = g.float() * grad_scale
+                st["s1"].mul_(self.b1).add_(gs, alpha=1 - self.b1)
+                st["s2"].mul_(self.b2).addcmul_(gs, gs, value=1 - self.b2)
+                r = (st["s1"] / float(bc1)) / (torch.sqrt(st["s2"]) / float(bc2) + self.eps) + st["wd"] * p
+                pn, rn, gn = (math.sqrt(float(x.detach().double().square().sum())) for x in (p, r, gs))
+                self._norms[i, 0], self._norms[i, 1], self._norms[i, 2] = pn, rn, gn
+                if st["adapt"] and pn > 0.0 and rn > 0.0:
+                    self._lr_scale[i] = pn / rn
+                step = np.float32(np.float32(lr) * np.float32(st["lr_mult"])) * np.float32(float(self._lr_scale[i]))
+                p.sub_(float(step) * r)
+                w16 = getattr(p, "bf16", None)
+                if w16 is not None:
+                    w16.copy_(p)
+                if "ema" in st:
+                    st["ema"].sub_((1 - d) * (st["ema"] - p))
                 continue
             g = g.float() * grad_scale + st["wd"] * p
             if self.clip > 0.0:
@@ -409,7 +466,8 @@ class FusedOptimizer:
         so momentum and LARS runs resume into each other; the slot name TensorFlow's own contrib LARS optimizer
         writes is not checked here (TensorFlow is not part of the test environment).  Adam -> <v>/Adam (m), <v>/Adam_1
         (v) and the scalars beta1_power, beta2_power (``beta_powers()``); parity of these names with a file written
-        by TensorFlow itself is not checked here either."""
+        by TensorFlow itself is not checked here either.  LAMB saves the same four names as Adam, so Adam and LAMB
+        runs resume into each other; parity with the names a TensorFlow LAMB writes is not checked."""
         out = []
         for p in self.params:
             name = getattr(p, "tf_name", None)
@@ -421,12 +479,12 @@ class FusedOptimizer:
             elif self.kind == "rmsprop":
                 out.append((name + "/RMSProp", st["s2"]))
                 out.append((name + "/RMSProp_1", st["s1"]))
-            elif self.kind == "adam":
+            elif self.kind in ADAM_LIKE:
                 out.append((name + "/Adam", st["s1"]))
                 out.append((name + "/Adam_1", st["s2"]))
             if "ema" in st:
                 out.append((name + "/ExponentialMovingAverage", st["ema"]))
-        if self.kind == "adam":
+        if self.kind in ADAM_LIKE:
             b1p, b2p = self.beta_powers()
             out.append(("beta1_power", torch.tensor(b1p)))
             out.append(("beta2_power", torch.tensor(b2p)))

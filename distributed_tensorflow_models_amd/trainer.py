@@ -112,6 +112,12 @@ ADAM_BSP_ONLY = ("--optimizer adam needs --sync_mode bsp (got %s): under asp / s
                  "which would need a shared count of applied updates per shard for the bias correction")
 
 
+LAMB_BSP_ONLY = ("--optimizer lamb needs --sync_mode bsp (got %s): under asp / ssp the update runs on owner shards, "
+                 "which hold neither whole tensors for the trust ratio nor a shared count of applied updates")
+LAMB_NO_CLIP = ("--optimizer lamb and --clip_global_norm are not combined: the global norm would have to leave the "
+                "decoupled decay term out, which the norm pass does not form")
+
+
 ACCUM_BSP_ONLY = ("--accum_steps > 1 needs --sync_mode bsp (got %s): under asp / ssp every push is applied by the "
                   "owner shards at once, so there is no step over which gradients could be summed")
 
@@ -204,14 +210,17 @@ def define_common_flags(flags, preset):
             ("num_epochs_per_decay", Fl, p["decay_epochs"], "Epochs after which learning rate decays."),
             ("learning_rate_decay_factor", Fl, p["decay_factor"], "Learning rate decay factor."),
             # large-batch training (all default to the preset's behaviour)
-            ("optimizer", S, "", "sgd | momentum | rmsprop | lars | adam (default: the preset's optimizer); lars and "
-             "adam are BSP only"),
-            ("adam_beta1", Fl, 0.9, "Adam: decay of the first-moment estimate"),
-            ("adam_beta2", Fl, 0.999, "Adam: decay of the second-moment estimate"),
+            ("optimizer", S, "", "sgd | momentum | rmsprop | lars | adam | lamb (default: the preset's optimizer); "
+             "lars, adam and lamb are BSP only; lamb is Adam's direction with a per-tensor trust ratio |w|/|update| "
+             "and uses the weight decay decoupled"),
+            ("adam_beta1", Fl, 0.9, "Adam and LAMB: decay of the first-moment estimate"),
+            ("adam_beta2", Fl, 0.999, "Adam and LAMB: decay of the second-moment estimate"),
             ("adam_epsilon", Fl, 1e-8, "Adam: epsilon added to sqrt(v)"),
+            ("lamb_epsilon", Fl, 1e-6, "LAMB: epsilon added to the bias-corrected sqrt(v)"),
             ("lars_eeta", Fl, 0.001, "LARS trust coefficient"),
             ("lars_epsilon", Fl, 0.0, "LARS epsilon in the trust ratio's denominator"),
-            ("clip_global_norm", Fl, 0.0, "clip the gradient by this global norm (0 = off); BSP only, not with lars"),
+            ("clip_global_norm", Fl, 0.0, "clip the gradient by this global norm (0 = off); BSP only, not with lars "
+             "or lamb"),
             ("warmup_steps", I, 0, "linear learning-rate warm-up from 0 over the first N steps (0 = off)"),
             ("lr_decay", S, "", "exponential (the preset's staircase decay, the default) | polynomial (from "
              "--initial_learning_rate to --end_learning_rate over --max_steps steps)"),
@@ -339,8 +348,9 @@ def train(preset, flags, default_mode="bsp"):
     mode = (FLAGS.sync_mode or default_mode).lower()
     logging.set_verbosity(logging.INFO)
     optimizer = (FLAGS.optimizer or cfg["optimizer"]).lower()
-    if optimizer not in ("sgd", "momentum", "rmsprop", "lars", "adam"):
-        raise ValueError("--optimizer must be sgd, momentum, rmsprop, lars or adam, got %r" % FLAGS.optimizer)
+    if optimizer not in ("sgd", "momentum", "rmsprop", "lars", "adam", "lamb"):
+        raise ValueError("--optimizer must be sgd, momentum, rmsprop, lars or adam, got %r (lamb is accepted too)"
+                         % FLAGS.optimizer)
     if FLAGS.lr_decay not in ("", "exponential", "polynomial"):
         raise ValueError("--lr_decay must be exponential or polynomial, got %r" % FLAGS.lr_decay)
     if mode in ("asp", "ssp") and (optimizer == "lars" or FLAGS.clip_global_norm > 0):
@@ -348,6 +358,10 @@ def train(preset, flags, default_mode="bsp"):
         raise ValueError(LARGE_BATCH_BSP_ONLY % mode)
     if mode in ("asp", "ssp") and optimizer == "adam":
         raise ValueError(ADAM_BSP_ONLY % mode)
+    if optimizer == "lamb" and mode in ("asp", "ssp"):
+        raise ValueError(LAMB_BSP_ONLY % mode)
+    if optimizer == "lamb" and FLAGS.clip_global_norm > 0:
+        raise ValueError(LAMB_NO_CLIP)
     accum = int(FLAGS.accum_steps)
     if accum < 1:
         raise ValueError("--accum_steps must be at least 1, got %d" % accum)
@@ -435,7 +449,8 @@ def train(preset, flags, default_mode="bsp"):
         sched = LinearWarmup(sched, FLAGS.warmup_steps)
     opt_kw = dict(optimizer=optimizer, lr=sched(0), momentum=cfg.get("momentum", 0.9),
                   rho=cfg.get("rmsprop_decay", 0.9),
-                  epsilon=FLAGS.adam_epsilon if optimizer == "adam" else cfg.get("rmsprop_epsilon", 1e-10))
+                  epsilon={"adam": FLAGS.adam_epsilon, "lamb": FLAGS.lamb_epsilon}.get(
+                      optimizer, cfg.get("rmsprop_epsilon", 1e-10)))
 
     # ---- engine + supervisor / checkpoints (C7, §5.4) -------------------------------------------
     from .compat.train import Supervisor, latest_checkpoint
@@ -641,17 +656,18 @@ def train(preset, flags, default_mode="bsp"):
             if summ is not None and summ_now:
                 summ.write(tbw, gs)
             extra = step_fn.timer.sections() if (mode == "bsp" and step_fn.timer is not None) else {}
-            if mode == "bsp" and step_fn.opt.scaled and (metrics.f is not None or (tbw is not None and summ_now)):
-                # the norm pass's results of this step (LARS / clipping only), read after the logged step's
+            if mode == "bsp" and step_fn.opt.normed and (metrics.f is not None or (tbw is not None and summ_now)):
+                # the norm pass's results of this step (LARS / clipping / LAMB only), read after the logged step's
                 # synchronisation above: no other step reads them on the host
                 ns = step_fn.opt.norm_stats()
                 if math.isfinite(ns["grad_norm"]) and tbw is not None and summ_now:
                     tbw.add_scalar("gradient_norm", ns["grad_norm"], gs)
-                    for k in ("lars/min_trust_ratio", "lars/max_trust_ratio"):
+                    for k in ("lars/min_trust_ratio", "lars/max_trust_ratio", "update_norm",
+                              "lamb/min_trust_ratio", "lamb/max_trust_ratio"):
                         if k in ns:
                             tbw.add_scalar(k, ns[k], gs)
                 extra.update(ns)
-            if mode == "bsp" and optimizer == "adam" and metrics.f is not None:
+            if mode == "bsp" and optimizer in ("adam", "lamb") and metrics.f is not None:
                 extra["adam_step"] = step_fn.opt.adam_step()  # applied updates: lags global_step after a NaN skip
             if mix_cfg is not None and metrics.f is not None:
                 extra["mix_lambda"] = step_fn.last_mix_lambda()  # mean own-label weight of this step (a host value)

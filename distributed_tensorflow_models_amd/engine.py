@@ -15,8 +15,10 @@ from .ops import fused as _fused
 from .ops import mix as _mix
 from .ops import nn as F
 from .ops import prune as _prune
+from .ops import sam as _sam
 from .ops.optim import FusedOptimizer
 from .ops.prune import PruneConfig  # noqa: F401  (TrainStep(prune=PruneConfig(...)))
+from .ops.sam import SamConfig  # noqa: F401  (TrainStep(sam=SamConfig(...)))
 from .parallel.bsp import BSPDataParallel, BufferSync
 from .utils.profiler import range_pop, range_push, roctx
 
@@ -139,7 +141,7 @@ class TrainStep:
                  grad_comm_dtype=None, ema_buffers=True, bn_sync_every=1, wgrad_stream=None, bsp_check=None,
                  overlap=True, force_comm=False, graph_comm=False, lars_eeta=0.001, lars_epsilon=0.0,
                  clip_global_norm=None, beta1=0.9, beta2=0.999, accum_steps=1, mix=None, rank=None,
-                 distill=None, prune=None, lars_skip=None):
+                 distill=None, prune=None, lars_skip=None, sam=None):
         # epsilon None: the optimizer's own default (1e-10; Adam 1e-8; LAMB 1e-6); beta1 / beta2: Adam and LAMB
         # lars_skip: predicate on a parameter, True = no trust ratio for it under lars / lamb (default: ndim <= 1)
         # accum_steps N: a call runs N micro-batches, sums their gradients (parallel/bsp.py begin_micro /
@@ -161,6 +163,18 @@ class TrainStep:
             raise ValueError("prune must be an ops.prune.PruneConfig or None, got %r" % (prune,))
         self.prune = prune
         self.pruner = None
+        # sam: an ops.sam.SamConfig - sharpness-aware minimisation.  Every micro-batch runs twice: forward and
+        # backward at the weights p (the ascent pass: rank-local, no collective), the perturbation p_hat = p + e(g)
+        # (SAM: e = rho*g/|g|; ASAM: scaled by p^2 element-wise), forward and backward at p_hat on the same batch with
+        # the same dropout masks, then p is put back bit for bit.  The descent gradient takes the ascent gradient's
+        # place in everything after (accumulate / fold, all-reduces, NaN guard, norm pass, optimizer); the BN moving
+        # statistics keep the ascent forward's update.  None: nothing is constructed, today's launches and bits.
+        if sam is not None and not isinstance(sam, SamConfig):
+            raise ValueError("sam must be an ops.sam.SamConfig or None, got %r" % (sam,))
+        if sam is not None and prune is not None:
+            raise ValueError("sam and prune are not combined: the perturbation would refill masked weights")
+        self.sam = sam
+        self.samp = None
         self.model = model
         if distill is not None and not isinstance(distill, DistillConfig):
             raise ValueError("distill must be an engine.DistillConfig or None, got %r" % (distill,))
@@ -220,6 +234,11 @@ class TrainStep:
             self.pruner = _prune.Pruner([(name, p.data, getattr(p, "bf16", None), self.opt.state[p].get("ema"))
                                          for name, p in pruned])
             self.pruner.params = [p for _name, p in pruned]  # for the checkpoint's <scope>/mask, <scope>/threshold
+        if sam is not None:
+            # after BufferSync (it may re-home the statistics into one flat buffer) and the optimizer: the tables
+            # hold raw pointers of the weights, their flat-buffer gradients, the bf16 copies and the statistics
+            self.samp = _sam.SamPerturber([(p.data, p.main_grad, getattr(p, "bf16", None)) for p in params],
+                                          moving_average_buffers(model), config=sam)
         if rank is None:
             import torch.distributed as dist
             rank = dist.get_rank(process_group) if dist.is_available() and dist.is_initialized() else 0
@@ -327,6 +346,23 @@ class TrainStep:
                 out.append([v[i * b:(i + 1) * b] for i in range(n)])
         return out[0], out[1]
 
+    def _forward_loss(self, images, labels, plan, tz):
+        """Training-mode forward and loss of one micro-batch (``plan``: its MixPlan or None; ``tz``: the teacher's
+        logits or None)."""
+        with roctx("forward"):
+            out = self.model(images, training=True)
+        with roctx("loss"):
+            if tz is not None:
+                return self.loss_fn(out, labels, plan, tz)
+            return self.loss_fn(out, labels) if plan is None else self.loss_fn(out, labels, plan)
+
+    def last_sam_norm(self):
+        """The ascent gradient's norm sqrt(S) of the last micro-batch (ops/sam.py; ASAM: of |p|*g).  Reads the
+        device: call on logged steps only.  None without SAM."""
+        if self.samp is None:
+            return None
+        return float(self.samp.last_norm())
+
     def _forward_backward(self, images, labels, plans=None):
         """One batch (two tensors), or the micro-batches of one step (two lists of tensors): micro-batches
         0 .. n-2 end in the accumulate launch, the last one folds and reduces.  ``plans`` (mixing only): one
@@ -348,6 +384,7 @@ class TrainStep:
             if images.is_cuda:
                 _fused.arena.begin_step(images.device)
                 _elementwise.advance_seed_offset(images.device)  # fresh dropout masks, replay included
+            perturbed = False
             try:
                 if plans is not None:
                     with roctx("mix"):
@@ -356,27 +393,61 @@ class TrainStep:
                 if self.distill is not None:
                     with roctx("teacher"):
                         tz = self._teacher_logits(images)
-                with roctx("forward"):
-                    out = self.model(images, training=True)
-                with roctx("loss"):
-                    if tz is not None:
-                        loss = self.loss_fn(out, labels, plans[i] if plans is not None else None, tz)
-                    else:
-                        loss = self.loss_fn(out, labels) if plans is None else self.loss_fn(out, labels, plans[i])
-                if last:
-                    self._mark("fwd")
-                    self.bufsync.issue()  # forward has finished every moving-statistics update
+                plan = plans[i] if plans is not None else None
+                if self.samp is not None:
+                    # SAM (ops/sam.py): the ascent pass at p on this rank's micro-batch (no collective), the
+                    # perturbation (which also clears the flat buffer), then the descent pass below at p_hat with the
+                    # same dropout masks; the BN statistics keep the ascent forward's update
+                    seed = _elementwise._seed[0]
+                    self.dp.begin_ascent()
+                    with roctx("sam_ascent"):
+                        loss_a = self._forward_loss(images, labels, plan, tz)
+                        if last:
+                            self.bufsync.issue()  # the statistics are final: the sync runs under both backwards
+                        else:
+                            self.bufsync.local_update()
+                        loss_a.backward()
+                        if images.is_cuda:
+                            _lib.side_join()
+                    self.dp.end_ascent()
+                    _fused.arena.end_step()
+                    with roctx("sam_perturb"):
+                        self.samp.perturb()  # (launches everything or, for a bad argument, nothing)
+                        perturbed = True
+                        if self.opt._dev is not None:
+                            F.refresh_flipped()
+                    _elementwise._seed[0] = seed
+                    if images.is_cuda:
+                        _fused.arena.begin_step(images.device)
+                    kl = len(self._kl_rows)
+                    loss = self._forward_loss(images, labels, plan, tz)
+                    del self._kl_rows[kl:]  # the reported loss and KL rows are the ascent pass's: taken at p
+                    if last:
+                        self._mark("fwd")
                 else:
-                    self.bufsync.local_update()  # one more local update for the last micro-batch's sync to cover
+                    loss = self._forward_loss(images, labels, plan, tz)
+                    if last:
+                        self._mark("fwd")
+                        self.bufsync.issue()  # forward has finished every moving-statistics update
+                    else:
+                        self.bufsync.local_update()  # one more local update for the last micro-batch's sync to cover
                 if self.on_backward is not None:
                     self.on_backward()
                 with roctx("backward"):  # bucket all-reduces are issued (own ranges) from the grad hooks
                     loss.backward()
                 if images.is_cuda:
                     _lib.side_join()  # weight gradients enqueued on the side stream (ops/_lib.py)
+                if perturbed:
+                    with roctx("sam_restore"):
+                        perturbed = False
+                        self.samp.restore()  # p, the bf16 copies and the BN statistics of the ascent pass, bit for bit
+                    loss = loss_a
                 if last:
                     self._mark("bwd")
             except BaseException:
+                self.dp.end_ascent()
+                if perturbed:
+                    self.samp.restore()
                 self.bufsync.abort()  # the live BN statistics stay this replica's own (never a partial sum)
                 raise
             finally:

@@ -118,6 +118,13 @@ _SIGS = {
     "dtm_multi_tensor_lamb": (_I, [_P, _P, _I, _P, _I, _D, _D, _D, _I, _P, _P, _P, _P, _P, _P, _P]),
     "dtm_check_finite": (None, [_P, _L, _P, _P]),
     "dtm_grad_accum": (_I, [_P, _P, _L, _I, _P, _P]),
+    "dtm_sam_chunk_size": (_I, []),
+    "dtm_sam_tensor_bytes": (_I, []),
+    "dtm_sam_chunk_bytes": (_I, []),
+    "dtm_sam_meta_bytes": (_I, []),
+    "dtm_sam_scratch_bytes": (_L, [_I, _I]),
+    "dtm_sam_perturb": (_I, [_P, _P, _I, _P, _I, _D, _I, _P, _P, _P]),
+    "dtm_sam_restore": (_I, [_P, _P, _I, _D, _P]),
     "dtm_prune_tensor_bytes": (_I, []),
     "dtm_prune_chunk_bytes": (_I, []),
     "dtm_prune_rec_bytes": (_I, []),

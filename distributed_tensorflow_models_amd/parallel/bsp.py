@@ -105,6 +105,7 @@ class BSPDataParallel:
         self.acc = None
         self.micro_flags = None
         self._micro = (0, 1)  # (index, count) of the micro-batch whose gradients the flat buffer is taking
+        self._ascent = False  # inside a backward whose gradients stay on this rank (begin_ascent / end_ascent)
 
     def _build_buckets(self):
         """Contiguous cap-sized buckets over the flat buffer, skipping the segments of windowed
@@ -200,6 +201,7 @@ class BSPDataParallel:
                 self.acc = torch.zeros_like(self.flat)
             self.micro_flags = torch.zeros(n, dtype=torch.int32, device=self.flat.device)
         self._micro = (i, n)
+        self._ascent = False
         if i == 0:
             self.flat.zero_()
             if n > 1:
@@ -207,6 +209,24 @@ class BSPDataParallel:
         self._have = [0] * len(self.buckets)
         self._launched = [False] * len(self.buckets)
         self._works = []
+        self._seen = set()
+        self.unreported = []
+
+    def begin_ascent(self):
+        """The backward that follows is rank-local (SAM's ascent pass, TrainStep(sam=...)): its ready notifications
+        are counted and checked as ever, but issue no collective.  Its gradients land in the flat buffer, which the
+        caller consumes and clears before the micro-batch's own backward."""
+        self._ascent = True
+
+    def end_ascent(self):
+        """After the rank-local backward (a no-op outside one): the ready bookkeeping starts over, as ``begin_micro``
+        leaves it, for the backward whose gradients count."""
+        if not self._ascent:
+            return
+        self._ascent = False
+        if any(self._launched) or self._works:
+            raise RuntimeError("a collective was issued during a rank-local backward")
+        self._have = [0] * len(self.buckets)
         self._seen = set()
         self.unreported = []
 
@@ -277,7 +297,8 @@ class BSPDataParallel:
         for bi, n in lst:
             self._have[bi] += n
             # (micro-batches before the last issue no collective: their gradients go to the accumulator)
-            if self.overlap and self._have[bi] == self.need[bi] and self._micro[0] == self._micro[1] - 1:
+            if self.overlap and self._have[bi] == self.need[bi] and self._micro[0] == self._micro[1] - 1 \
+                    and not self._ascent:
                 self._launch(bi)
 
     def _launch(self, bi):

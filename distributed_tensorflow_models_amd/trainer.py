@@ -152,6 +152,32 @@ def prune_config(FLAGS, mode):
                        FLAGS.prune_frequency, FLAGS.prune_exponent, select)
 
 
+SAM_BSP_ONLY = ("--sam_rho needs --sync_mode bsp (got %s): under asp / ssp the step is the parameter store's, which "
+                "has no place for a second pass at perturbed weights")
+SAM_NO_PRUNE = ("--sam_rho and --prune_sparsity are not combined: the perturbation would refill masked weights")
+SAM_NO_QUANTIZE = ("--sam_rho and --quantize are not combined: the fake-quantised weights are derived outside the "
+                   "compute copies that the perturbation maintains")
+
+
+def sam_config(FLAGS, mode):
+    """The SamConfig of --sam_rho / --sam_adaptive, or None with --sam_rho 0 (checked before any process group
+    exists)."""
+    import math
+    rho = float(FLAGS.sam_rho)
+    if not math.isfinite(rho) or rho < 0.0:
+        raise ValueError("--sam_rho must be a finite number, at least 0, got %r" % (FLAGS.sam_rho,))
+    if rho == 0.0:
+        return None
+    if mode in ("asp", "ssp"):
+        raise ValueError(SAM_BSP_ONLY % mode)
+    if FLAGS.prune_sparsity:
+        raise ValueError(SAM_NO_PRUNE)
+    if "quantize" in FLAGS and FLAGS.quantize:
+        raise ValueError(SAM_NO_QUANTIZE)
+    from .ops.sam import SamConfig
+    return SamConfig(rho, bool(FLAGS.sam_adaptive))
+
+
 def parse_model_kw(text):
     """"k=v,..." -> {k: int or float}: the numeric model keywords of --distill_teacher_kw."""
     out = {}
@@ -254,6 +280,10 @@ def define_common_flags(flags, preset):
             ("prune_exponent", Fl, 3.0, "exponent of the sparsity schedule"),
             ("prune_exclude", S, "", "regular expression: variables whose TF name it matches stay dense (usually "
              "the first conv and the logits)"),
+            # sharpness-aware minimisation (ops.sam.SamConfig; BSP only)
+            ("sam_rho", Fl, 0.0, "radius of the SAM perturbation: every micro-batch runs twice, the update takes the "
+             "gradient at p + rho * g / |g| (0 = off; usual starting values: 0.05, with --sam_adaptive 0.5 - 2)"),
+            ("sam_adaptive", B, False, "ASAM: the perturbation is scaled element-wise by p^2 (scale-invariant)"),
             ("sync_mode", S, "", "bsp | asp | ssp (default from the entry script)"),
             ("max_staleness", I, 5, "SSP staleness bound in local steps"),
             ("synthetic_data", B, False, "use HBM-resident synthetic batches"),
@@ -375,6 +405,7 @@ def train(preset, flags, default_mode="bsp"):
         mix_cfg = MixConfig(FLAGS.mixup_alpha, FLAGS.cutmix_alpha, FLAGS.mix_prob, FLAGS.mix_switch_prob,
                             FLAGS.mix_per_row, seed=FLAGS.seed)
     prune_cfg = prune_config(FLAGS, mode)
+    sam_cfg = sam_config(FLAGS, mode)
     distill_ckpt = distill_kw = None
     if FLAGS.distill_teacher:
         if mode in ("asp", "ssp"):
@@ -502,7 +533,7 @@ def train(preset, flags, default_mode="bsp"):
                             else None, lars_eeta=FLAGS.lars_eeta, lars_epsilon=FLAGS.lars_epsilon,
                             clip_global_norm=FLAGS.clip_global_norm if FLAGS.clip_global_norm > 0 else None,
                             beta1=FLAGS.adam_beta1, beta2=FLAGS.adam_beta2, accum_steps=accum, mix=mix_cfg, rank=rank,
-                            distill=distill_cfg, prune=prune_cfg, **opt_kw)
+                            distill=distill_cfg, prune=prune_cfg, sam=sam_cfg, **opt_kw)
         # (the pruner's <scope>/mask and <scope>/threshold in front of the global step, which stays last)
         vars_ = model_variables(model, step_fn.opt, gstep, pruner=step_fn.pruner, **ckpt_kw)
         vars_[-1].name = cfg.get("global_step_name", "global_step")
@@ -673,6 +704,8 @@ def train(preset, flags, default_mode="bsp"):
                 extra["mix_lambda"] = step_fn.last_mix_lambda()  # mean own-label weight of this step (a host value)
             if distill_cfg is not None and metrics.f is not None:
                 extra["distill_kl"] = step_fn.last_distill_kl()  # a device read, after the synchronisation above
+            if sam_cfg is not None and metrics.f is not None:
+                extra["sam_grad_norm"] = step_fn.last_sam_norm()  # a device read, after the synchronisation above
             if prune_cfg is not None and metrics.f is not None:
                 # a device read, after the synchronisation above
                 extra["sparsity"], extra["prune_target"] = step_fn.last_sparsity()

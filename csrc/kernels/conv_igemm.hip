@@ -85,6 +85,15 @@ struct ConvNTArgs {
     bf16_t* y;
     int off, K;
   } split[8];
+  // block-output prologue of conv_nt_kernel<..., BO> (dtm_conv_fwd_bn_blockout): x is the RAW last conv of the
+  // previous bottleneck unit; the conv forms that unit's output y = relu(x*scale + shift + res') itself while it
+  // stages its operand (res' = res, or res*rscale + rshift for a BN'd shortcut), stores y and its ReLU bitmask
+  // once as a side output and multiplies by it - the separate BN-apply pass and the re-read of y disappear
+  const bf16_t* bo_res = nullptr;  // [M][C] residual (same rows / channels as x)
+  const float* bo_ss = nullptr;    // [>= 2][C]: scale, shift of x
+  const float* bo_rss = nullptr;   // nullptr (identity residual) or [>= 2][C]: scale, shift of res
+  bf16_t* bo_y = nullptr;          // [M][C] out
+  uint8_t* bo_mask = nullptr;      // nullptr or [M*C/8] out: bit e of byte (row*C + c)/8 = [y > 0] of channel c + e
 };
 
 // block -> (class, tile) of a grouped launch (XCD remap over the whole grid; class = z-slice of the logical
@@ -459,7 +468,9 @@ __device__ __forceinline__ void conv_nt_epilogue(const ConvNTArgs& a, f32x4 (&ac
 
 // LBW: minimum waves per SIMD the register allocation must allow (__launch_bounds__; 0 = none), EG: epilogue side-input
 // row group - the occupancy variants of the register-staged dgrads with post-ops (A/B knob dtm_conv_set_act_occ)
-template <int PT, int CT, int WP, int WC, int UD, int NBUF, bool SPL = false, int LBW = 0, int EG = 4>
+// BO: the block-output prologue (ConvNTArgs::bo_*; 1x1 stride-1 forwards with ONE channel tile, so every element of
+// y is gathered - and stored - exactly once): 1 = plain, 2 = non-temporal loads of the two streamed inputs
+template <int PT, int CT, int WP, int WC, int UD, int NBUF, bool SPL = false, int LBW = 0, int EG = 4, int BO = 0>
 __global__ __launch_bounds__(256, LBW > 0 ? LBW : 1) void conv_nt_kernel(ConvNTArgs a) {
   constexpr int BK = 64;
   constexpr int NWP = PT / WP;
@@ -470,9 +481,11 @@ __global__ __launch_bounds__(256, LBW > 0 ? LBW : 1) void conv_nt_kernel(ConvNTA
   constexpr int WCH = CT / 32;
   constexpr int BUF = (PT + CT) * 128;
   constexpr int MAXC = 512;  // prologue scale/shift staged in LDS for C <= MAXC (bottleneck widths)
-  __shared__ __attribute__((aligned(16))) char smem[NBUF * BUF + MAXC * 8];
+  __shared__ __attribute__((aligned(16))) char smem[NBUF * BUF + MAXC * 8 * (BO ? 2 : 1)];
   float* s_scale = (float*)(smem + NBUF * BUF);
   float* s_shift = s_scale + MAXC;
+  float* s_rscale = s_shift + MAXC;  // (BO only: scale / shift of a BN'd residual, 1 / 0 for an identity one)
+  float* s_rshift = s_rscale + MAXC;
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wp = wave % NWP, wc = wave / NWP;
@@ -485,8 +498,18 @@ __global__ __launch_bounds__(256, LBW > 0 ? LBW : 1) void conv_nt_kernel(ConvNTA
     for (int c = tid; c < a.C; c += 256) { s_scale[c] = a.in_scale[c]; s_shift[c] = a.in_shift[c]; }
     __syncthreads();
   }
+  if constexpr (BO != 0) {  // (C <= MAXC: checked by the host)
+    for (int c = tid; c < a.C; c += 256) {
+      s_scale[c] = a.bo_ss[c];
+      s_shift[c] = a.bo_ss[a.C + c];
+      s_rscale[c] = a.bo_rss ? a.bo_rss[c] : 1.f;
+      s_rshift[c] = a.bo_rss ? a.bo_rss[a.C + c] : 0.f;
+    }
+    __syncthreads();
+  }
 
   const __amdgpu_buffer_rsrc_t xr = make_rsrc(a.x, a.x_bytes);
+  const __amdgpu_buffer_rsrc_t resr = make_rsrc(BO ? (const void*)a.bo_res : (const void*)a.x, a.x_bytes);
   const __amdgpu_buffer_rsrc_t wr = make_rsrc(a.w, a.w_bytes);
 
   // per-row pixel decode (rows rb + 32*i of the pixel tile)
@@ -518,6 +541,7 @@ __global__ __launch_bounds__(256, LBW > 0 ? LBW : 1) void conv_nt_kernel(ConvNTA
   // at 128x128 and is 20-60 % slower at 128x64 from the lost occupancy)
   struct Stage {
     uint4 a[ACH], w[WCH];
+    uint4 r[BO ? ACH : 1];  // (BO: the residual chunk of every activation chunk)
     bool v[ACH];
     int c;  // channel of this stage's activation chunk (for the prologue affine)
   };
@@ -534,7 +558,14 @@ __global__ __launch_bounds__(256, LBW > 0 ? LBW : 1) void conv_nt_kernel(ConvNTA
       int ih = UD > 1 ? ihv / UD : ihv, iw = UD > 1 ? iwv / UD : iwv;
       uint32_t off = v ? (uint32_t)((pixbase[i] + ih * a.Win + iw) * a.pix_bytes + cc * 2) : OOB_OFFSET;
       st.v[i] = v;
-      st.a[i] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(xr, off, 0, 0));
+      if constexpr (BO == 2) {
+        st.a[i] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(xr, off, 0, 2));
+        st.r[i] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(resr, off, 0, 2));
+      } else {
+        st.a[i] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(xr, off, 0, 0));
+        if constexpr (BO == 1)
+          st.r[i] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(resr, off, 0, 0));
+      }
     }
 #pragma unroll
     for (int i = 0; i < WCH; ++i) {
@@ -553,6 +584,53 @@ __global__ __launch_bounds__(256, LBW > 0 ? LBW : 1) void conv_nt_kernel(ConvNTA
 
   auto swrite = [&](int buf, Stage& st) {
     char* base = smem + buf * BUF;
+    if constexpr (BO != 0) {
+      // the previous unit's block output, formed here in bn_apply_fast's operation order (bit-identical y and mask),
+      // stored once and used as this conv's operand.  1x1 stride 1 without padding: tile row = pixel = row of y;
+      // rows >= M and k >= Kg are invalid chunks and store nothing
+      // (4 channels at a time: the parameters of a half chunk are 16 registers live instead of 32 - the 128-row tile
+      // keeps its 3 waves / SIMD without scratch)
+      uint32_t bits[ACH];
+#pragma unroll
+      for (int i = 0; i < ACH; ++i) bits[i] = 0u;
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const float4 s4 = *(const float4*)(s_scale + st.c + 4 * h), h4 = *(const float4*)(s_shift + st.c + 4 * h);
+        const float4 t4 = *(const float4*)(s_rscale + st.c + 4 * h), g4 = *(const float4*)(s_rshift + st.c + 4 * h);
+        const float sc[4] = {s4.x, s4.y, s4.z, s4.w}, sh[4] = {h4.x, h4.y, h4.z, h4.w};
+        const float rsc[4] = {t4.x, t4.y, t4.z, t4.w}, rsh[4] = {g4.x, g4.y, g4.z, g4.w};
+#pragma unroll
+        for (int i = 0; i < ACH; ++i) {
+          if (st.v[i]) {
+            const uint32_t u[2] = {h ? st.a[i].z : st.a[i].x, h ? st.a[i].w : st.a[i].y};
+            const uint32_t q[2] = {h ? st.r[i].z : st.r[i].x, h ? st.r[i].w : st.r[i].y};
+            float f[4];
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+              f[2 * e] = fmaf(lo_bf(u[e]), sc[2 * e], sh[2 * e]);
+              f[2 * e + 1] = fmaf(hi_bf(u[e]), sc[2 * e + 1], sh[2 * e + 1]);
+              f[2 * e] += fmaf(lo_bf(q[e]), rsc[2 * e], rsh[2 * e]);
+              f[2 * e + 1] += fmaf(hi_bf(q[e]), rsc[2 * e + 1], rsh[2 * e + 1]);
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              bits[i] |= (f[e] > 0.f ? 1u : 0u) << (4 * h + e);
+              f[e] = fmaxf(f[e], 0.f);
+            }
+            if (h) { st.a[i].z = pack2bf(f[0], f[1]); st.a[i].w = pack2bf(f[2], f[3]); }
+            else { st.a[i].x = pack2bf(f[0], f[1]); st.a[i].y = pack2bf(f[2], f[3]); }
+          }
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < ACH; ++i) {
+        if (st.v[i]) {
+          const size_t o = (size_t)(p0 + rb + 32 * i) * a.C + st.c;
+          *(uint4*)(a.bo_y + o) = st.a[i];
+          if (a.bo_mask) a.bo_mask[o >> 3] = (uint8_t)bits[i];
+        }
+      }
+    }
     if (a.in_scale) {
       // fused BatchNorm-apply + ReLU of the previous layer on the gathered input
       float sc[8], sh[8];
@@ -2739,10 +2817,10 @@ static bool stream_ok(const ConvNTArgs& a) {
          (!a.in_scale || a.C <= 512) && a.dump != nullptr && a.ostr == 1;
 }
 
-template <int PT, int CT, int WP, int WC, int UD, int NBUF = 2, bool SPL = false, int LBW = 0, int EG = 4>
+template <int PT, int CT, int WP, int WC, int UD, int NBUF = 2, bool SPL = false, int LBW = 0, int EG = 4, int BO = 0>
 static void launch_nt(const ConvNTArgs& a, hipStream_t st) {
   dim3 grid((a.K + CT - 1) / CT, (a.M + PT - 1) / PT, a.ngrp > 1 ? a.ngrp : 1);
-  hipLaunchKernelGGL((conv_nt_kernel<PT, CT, WP, WC, UD, NBUF, SPL, LBW, EG>), grid, dim3(256), 0, st, a);
+  hipLaunchKernelGGL((conv_nt_kernel<PT, CT, WP, WC, UD, NBUF, SPL, LBW, EG, BO>), grid, dim3(256), 0, st, a);
 }
 // Occupancy variants of the register-staged 64x128 / 128x64 tiles (A/B knobs; DTM_ACT_OCC / DTM_NT_OCC set the initial
 // values): 0 = as compiled (128 VGPR + 32 AGPR: 3 waves/SIMD), 1 = epilogue side rows 2 at a time, 2 = 4 waves/SIMD
@@ -3003,9 +3081,35 @@ DTM_API int dtm_get_deterministic();
 static int g_split_tile = 1;  // A/B knob: the merged-head tile rule in conv_fwd_impl (dtm_conv_set_split_tile)
 DTM_API void dtm_conv_set_split_tile(int on) { g_split_tile = on; }
 
+// The block-output prologue (conv_nt_kernel<..., BO>, dtm_conv_fwd_bn_blockout).  A/B knob dtm_conv_set_blockout:
+// mode -1 = the policy (every eligible launch), 0 = never (the entry point declines: the caller runs the BN-apply
+// and the plain conv), 1 = every eligible launch, 2 / 3 = only on the 128x64 / the 64x128 tile (ResNet-50's block-1 /
+// block-2 shapes apart); nt = non-temporal loads of the two streamed inputs.
+static int g_blockout = -1, g_blockout_nt = 1;
+DTM_API void dtm_conv_set_blockout(int mode, int nt) { g_blockout = mode; g_blockout_nt = nt; }
+struct BlockOut {
+  const void* res;
+  const float* ss;
+  const float* rss;
+  void* y;
+  void* mask;
+};
+constexpr int DTM_DECLINED = 1;  // not an error: the fused form does not apply to this launch, nothing was launched
+static void launch_blockout(const ConvNTArgs& a, int tile, hipStream_t st) {
+  // the tiles of launch_nt_act's forward-with-statistics variant, held at its 3 waves / SIMD
+  if (tile == 3) {
+    if (g_blockout_nt) launch_nt<128, 64, 32, 64, 1, 1, false, 3, 4, 2>(a, st);
+    else launch_nt<128, 64, 32, 64, 1, 1, false, 3, 4, 1>(a, st);
+  } else {
+    if (g_blockout_nt) launch_nt<64, 128, 32, 64, 1, 1, false, 3, 4, 2>(a, st);
+    else launch_nt<64, 128, 32, 64, 1, 1, false, 3, 4, 1>(a, st);
+  }
+}
+
 static int conv_fwd_impl(const void* x, const void* w, void* y, bool stats, const float* bias, const float* in_scale,
                          const float* in_shift, int relu, const ConvDesc* d, hipStream_t stream, float** rows_ws,
-                         int* nrows, const ConvNTArgs::Split* split = nullptr, int nsplit = 0) {
+                         int* nrows, const ConvNTArgs::Split* split = nullptr, int nsplit = 0,
+                         const BlockOut* bo = nullptr) {
   if (!dtm_device_ok()) return -9;
   if (d->C % 8 || d->K % 4) return -1;
   ConvNTArgs a;
@@ -3047,6 +3151,19 @@ static int conv_fwd_impl(const void* x, const void* w, void* y, bool stats, cons
   // head shape (tools/split_tile_sweep.py, profiles/r4/r4_split_tile_sweep.log): 799 -> ~765 us per step, e.g.
   // 17x17 768 -> 640 85 -> 77 us, 35x35 288 -> 240 84 -> 80 us (the policy's 64x128 / 128x64 picks)
   if (nsplit > 0 && g_split_tile && g_tile_env < 0 && tc.id != 40 && tc.id != 21) tc = {21, 128, 2};
+  if (bo) {
+    // eligibility of the block-output prologue (decided before anything is launched): a 1x1 stride-1 unpadded conv on
+    // the register-staged 128x64 / 64x128 tile with ONE channel tile (each element of y gathered exactly once), dense
+    // input rows, the prologue parameters in LDS, no other prologue / epilogue option
+    const int ct = tc.id == 3 ? 64 : 128;
+    if (g_blockout == 0 || (tc.id != 3 && tc.id != 4) || (g_blockout == 2 && tc.id != 3) ||
+        (g_blockout == 3 && tc.id != 4) || a.K > ct || a.R != 1 || a.S != 1 || a.stride != 1 ||
+        a.pad_h || a.pad_w || a.P != a.Hin || a.Q != a.Win || a.C % 8 || a.C > 512 || a.pix_bytes != a.C * 2 ||
+        bias || relu || in_scale || nsplit > 0 || !stats || !bo->res || !bo->ss || !bo->y)
+      return DTM_DECLINED;
+    a.bo_res = (const bf16_t*)bo->res; a.bo_ss = bo->ss; a.bo_rss = bo->rss;
+    a.bo_y = (bf16_t*)bo->y; a.bo_mask = (uint8_t*)bo->mask;
+  }
   if (tc.id == 60) direct_setup(a);
   if (stats) {
     // one per streaming / direct worker; one per pixel tile (staged epilogue, K % 8 == 0); else per (pixel
@@ -3058,7 +3175,8 @@ static int conv_fwd_impl(const void* x, const void* w, void* y, bool stats, cons
     if (!ws) return -4;
     a.stats = ws;
   }
-  dispatch_nt(a, 1, tc, stream);
+  if (bo) launch_blockout(a, tc.id, stream);
+  else dispatch_nt(a, 1, tc, stream);
   *rows_ws = a.stats;
   *nrows = rows;
   return 0;
@@ -3122,6 +3240,25 @@ DTM_API int dtm_conv_fwd_bn(const void* x, const void* w, void* y, const float* 
   float* ws = nullptr;
   int rows = 0;
   int rc = conv_fwd_impl(x, w, y, true, nullptr, in_scale, in_shift, 0, d, (hipStream_t)stream, &ws, &rows);
+  if (rc) return rc;
+  return dtm_bn_stats_finalize(ws, rows, d->K, gamma, beta, mov_mean, mov_var, ss, count, eps, decay, update, bessel,
+                               (hipStream_t)stream);
+}
+
+// dtm_conv_fwd_bn whose input is a bottleneck unit's output that has not been formed yet: the conv computes
+// y = relu(raw3*ss3.scale + ss3.shift + res [*res_ss.scale + res_ss.shift]) in its operand staging (what
+// dtm_bn_apply2 computes, bit for bit), stores y and its ReLU bitmask (mask may be null) and convolves y.
+// Returns 1 (declined, nothing launched) when the launch is not eligible (conv_fwd_impl): the caller then runs
+// dtm_bn_apply2 and dtm_conv_fwd_bn.
+DTM_API int dtm_conv_fwd_bn_blockout(const void* raw3, const float* ss3, const void* res, const float* res_ss, void* y,
+                                     void* mask, const void* w, void* out, const float* gamma, const float* beta,
+                                     float* mov_mean, float* mov_var, float* ss, float count, float eps, float decay,
+                                     int update, int bessel, const ConvDesc* d, void* stream) {
+  float* ws = nullptr;
+  int rows = 0;
+  const BlockOut bo = {res, ss3, res_ss, y, mask};
+  int rc = conv_fwd_impl(raw3, w, out, true, nullptr, nullptr, nullptr, 0, d, (hipStream_t)stream, &ws, &rows, nullptr,
+                         0, &bo);
   if (rc) return rc;
   return dtm_bn_stats_finalize(ws, rows, d->K, gamma, beta, mov_mean, mov_var, ss, count, eps, decay, update, bessel,
                                (hipStream_t)stream);

@@ -176,8 +176,9 @@ class Conv2d(Layer):
             use_bias = normalizer is None
         self.biases = make_param((cout,), _join(scope, "biases"), ("constant", bias_init)) if use_bias else None
 
-    def forward(self, x, training=True, residual=None, residual_act=None):
+    def forward(self, x, training=True, residual=None, residual_act=None, defer_out=False):
         """residual: added after normalisation, before `residual_act` (ResNet unit output).
+        defer_out (with a residual, HIP path): the output may be a lazy.DeferredBlockOut (ResNet's BottleneckV1).
 
         On the HIP path a conv+BN returns a LazyBN (statistics from the conv epilogue, normalisation
         folded into the consumer); see ops.fused."""
@@ -185,7 +186,7 @@ class Conv2d(Layer):
             relu = self.activation == "relu" and residual is None
             lazy = fused.conv_bn(x, self.weights, self.bn, self.stride, self.padding, training, relu)
             if residual is not None:
-                return lazy.materialize(residual=residual, residual_act=residual_act)
+                return lazy.materialize(residual=residual, residual_act=residual_act, defer=defer_out)
             if self.activation in ("relu", None):
                 return lazy
             return apply_activation(lazy.materialize(), self.activation)

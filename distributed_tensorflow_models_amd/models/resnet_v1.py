@@ -16,7 +16,8 @@ import torch
 
 from ..ops import nn as F
 from ..ops import fused
-from ..ops.lazy import Subsampled, as_tensor
+from ..ops import features
+from ..ops.lazy import DeferredBlockOut, Subsampled, as_tensor
 from .layers import Conv2d, Layer, _join, apply_activation, fused_enabled
 
 
@@ -65,7 +66,23 @@ class BottleneckV1(Layer):
                             conv2d_same_padding(3, stride, rate), "relu", bn, None, wd, init, rate=rate)
         self.conv3 = Conv2d(_join(scope, "conv3"), depth_bottleneck, depth, 1, 1, "SAME", None, bn, None, wd, init)
 
-    def forward(self, x, training=True, end_points=None):
+    def forward(self, x, training=True, end_points=None, defer_out=False):
+        """defer_out: the caller's next op is an identity unit (its 1x1 stride-1 conv1 reads this unit's output first):
+        on the training HIP path the output is then a ``DeferredBlockOut`` - its BN-apply launch is left to that conv1,
+        which forms it in its operand staging (feature blockout_conv_fuse)."""
+        defer_out = (defer_out and training and end_points is None and x.is_cuda and
+                     features.on("blockout_conv_fuse"))
+        if isinstance(x, DeferredBlockOut):
+            if self.shortcut is not None or end_points is not None:
+                x = as_tensor(x)
+            else:
+                # conv1 fills the block input (or the ordinary BN-apply does, where conv1 is not eligible); the
+                # identity shortcut below then reads the filled tensor
+                r1 = self.conv1(x, training)
+                x = as_tensor(x)
+                sc = subsample(x, self.stride, lazy=self.conv3.bn is not None)
+                r2 = self.conv2(r1, training)
+                return self.conv3(r2, training, residual=sc, residual_act="relu", defer_out=defer_out)
         if self.shortcut is not None:
             # projection shortcut and conv1: sibling 1x1 conv+BNs of x with one merged backward (ops.fused).  (A merged
             # FORWARD, as Inception's heads have, was measured +0.31..+0.41 % step here - the 512 + 128 -> 640-channel
@@ -88,7 +105,14 @@ class BottleneckV1(Layer):
                 end_points[c.scope] = as_tensor(v)
             end_points[self.scope] = y
             return y
-        return self.conv3(r2, training, residual=sc, residual_act="relu")
+        return self.conv3(r2, training, residual=sc, residual_act="relu", defer_out=defer_out)
+
+
+def _unobserved(u):
+    """The unit's forward is BottleneckV1's own and nothing hooks the module: a wrapped forward or a module hook
+    observes the unit's input / output and must see filled tensors, so no deferred output passes such a unit."""
+    return (type(u).forward is BottleneckV1.forward and "forward" not in vars(u) and not u._forward_hooks and
+            not u._forward_pre_hooks)
 
 
 def stack_blocks_plan(blocks, output_stride=None, store_non_strided_activations=False):
@@ -190,7 +214,17 @@ class ResNetV1(Layer):
             net = F.max_pool(net, 3, 2, "SAME")
         ends = {i: (name, sub) for i, name, sub in self.block_ends}
         for i, u in enumerate(self.units):
-            net = u(net, training, end_points) if end_points is not None else u(net, training)
+            # the unit's output stays unfilled for the next unit's conv1 to form (BottleneckV1.forward) when that unit
+            # is an identity unit of the same block; block ends and inputs of projection units are filled tensors
+            nxt = self.units[i + 1] if (i + 1 < len(self.units) and i not in ends) else None
+            defer = (nxt is not None and nxt.shortcut is None and end_points is None and _unobserved(u) and
+                     _unobserved(nxt))
+            if end_points is not None:
+                net = u(net, training, end_points)
+            else:
+                net = u(net, training, defer_out=True) if defer else u(net, training)
+            if i in ends or nxt is None or nxt.shortcut is not None:
+                net = as_tensor(net)
             if i in ends:
                 name, sub = ends[i]
                 if end_points is not None:

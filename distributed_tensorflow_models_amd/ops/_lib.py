@@ -163,6 +163,8 @@ _SIGS = {
     "dtm_set_reserved_cus": (None, [_I]),
     "dtm_stats_combine_multi": (_I, [_P, _P, _I, _F, _P, _L, _I, _P]),
     "dtm_conv_fwd_bn_multi": (_I, [_P, _P, _P, _P, _I, _P, _F, _F, _F, _I, _I, ctypes.POINTER(ConvDesc), _P]),
+    "dtm_conv_fwd_bn_blockout": (_I, [_P] * 13 + [_F, _F, _F, _I, _I, ctypes.POINTER(ConvDesc), _P]),
+    "dtm_conv_set_blockout": (None, [_I, _I]),
     "dtm_conv_set_dec_lpt": (None, [_I]),
     "dtm_conv_set_dec_tile": (None, [_I]),
     "dtm_conv_set_split_tile": (None, [_I]),

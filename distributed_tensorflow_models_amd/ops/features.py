@@ -34,6 +34,9 @@ FEATURES = {
                      "(TrainStep(wgrad_stream=...) overrides per model)", "profiles/ab/r3_ab_wgrad_side_stream.log"),
     "pool_tail": ("Inception's aux-head pool gradient added in place into the Mixed_6e-output gradient the main path "
                   "returned (no separate add over the 17x17x768 map)", "profiles/ab/r5_ab_pool_tail.log"),
+    "blockout_conv_fuse": ("forward only: a ResNet identity unit's 1x1 conv1 forms the previous unit's output "
+                           "relu(bn(raw) + shortcut) in its operand staging and stores it as a side output (no separate "
+                           "BN-apply pass, no re-read); routes no gradient", "profiles/ab/ab_blockout_conv_fuse.log"),
     "bsp_compact": ("dead-tap conv weights get a compact all-reduce bucket holding their live window only",
                     "tests/test_distributed.py test_bsp_dead_tap_gradients_left_out_of_the_allreduce"),
 }

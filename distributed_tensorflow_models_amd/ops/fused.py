@@ -16,7 +16,7 @@ import torch
 
 from . import _lib, features
 from .geometry import conv_geom
-from .lazy import LazyBN, Subsampled, as_tensor  # noqa: F401
+from .lazy import DeferredBlockOut, LazyBN, Subsampled, as_tensor  # noqa: F401
 from .nn import _accum_param_grad, _check, _notify, dgrad_decomposable, grad_target, weight_bf16, weight_flipped
 
 
@@ -93,6 +93,29 @@ class _BNOutInfo:
 
 
 BNOUT_FUSED = [0]  # count of block-output BN backwards absorbed by a dgrad epilogue (tests / diagnostics)
+BLOCKOUT_FUSED = [0]  # count of block-output BN-applies formed by the consuming conv's forward (tests / diagnostics)
+
+
+class _DeferState:
+    """Launch parameters of a deferred block-output BN-apply (``y._dtm_defer`` until y is filled, see
+    lazy.DeferredBlockOut): y = relu(x*ss.scale + ss.shift + res [*res_ss.scale + res_ss.shift]) and its bitmask."""
+    __slots__ = ("x", "ss", "res", "res_ss", "mask", "res_mode")
+
+    def __init__(self, x, ss, res, res_ss, mask, res_mode):
+        self.x, self.ss, self.res, self.res_ss, self.mask, self.res_mode = x, ss, res, res_ss, mask, res_mode
+
+
+def blockout_fill(y):
+    """Fill a deferred block output with the ordinary BN-apply kernel (its first consumer is not the eligible conv);
+    a no-op on a filled tensor."""
+    st = getattr(y, "_dtm_defer", None)
+    if st is None:
+        return
+    y._dtm_defer = None
+    C = y.shape[-1]
+    _check(_lib.lib().dtm_bn_apply2(_lib.ptr(st.x), _lib.ptr(st.ss), _lib.ptr(st.res), _lib.ptr(st.res_ss), _lib.ptr(y),
+                                    _lib.ptr(st.mask), y.numel() // C, C, st.res_mode, 1, _lib.stream_ptr()),
+           "bn_apply")
 
 
 def _bnout_enabled():
@@ -241,7 +264,29 @@ class _ConvBNFn(torch.autograd.Function):
         else:
             x_raw = None
         ss = None
-        if bn is not None:
+        # the input is a block output whose BN-apply launch was deferred to this conv (lazy.DeferredBlockOut): the
+        # conv forms it in its operand staging and stores it (and the ReLU bitmask) as a side output; where the
+        # kernel declines (shape / tile / policy: rc 1, nothing launched) the ordinary BN-apply fills it first
+        defer = getattr(x, "_dtm_defer", None) if (in_ss is None and x_mat is None) else None
+        if defer is not None and bn is not None:
+            ss = torch.empty((4, geom.K), device=x.device, dtype=torch.float32)
+            count = float(geom.N * geom.P * geom.Q)
+            rc = L.dtm_conv_fwd_bn_blockout(_lib.ptr(defer.x), _lib.ptr(defer.ss), _lib.ptr(defer.res),
+                                            _lib.ptr(defer.res_ss), _lib.ptr(x), _lib.ptr(defer.mask), _lib.ptr(w16),
+                                            _lib.ptr(y), _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(bn.moving_mean),
+                                            _lib.ptr(bn.moving_variance), _lib.ptr(ss), count, float(bn.eps),
+                                            float(bn.decay), 1, int(bn.bessel), ctypes.byref(d), s)
+            if rc == 0:
+                x._dtm_defer = None
+                BLOCKOUT_FUSED[0] += 1
+            elif rc != 1:
+                _check(rc, "conv_fwd_bn_blockout")
+        if defer is not None and getattr(x, "_dtm_defer", None) is not None:
+            blockout_fill(x)
+            defer = None
+        if defer is not None:
+            ctx.count = count
+        elif bn is not None:
             ss = torch.empty((4, geom.K), device=x.device, dtype=torch.float32)
             count = float(geom.N * geom.P * geom.Q)
             _check(L.dtm_conv_fwd_bn(_lib.ptr(x), _lib.ptr(w16), _lib.ptr(y), _lib.ptr(sc), _lib.ptr(sh),
@@ -494,7 +539,7 @@ class _BNApplyFn(torch.autograd.Function):
     unscaled: bit 0 / bit 1 = x / the BN'd residual comes from a training conv+BN (LazyBN.unscaled)."""
 
     @staticmethod
-    def forward(ctx, x, ss, res, res_ss, relu, res_slot=None, res_stride=1, unscaled=0):
+    def forward(ctx, x, ss, res, res_ss, relu, res_slot=None, res_stride=1, unscaled=0, defer=False):
         L = _lib.lib()
         C = x.shape[-1]
         M = x.numel() // C
@@ -503,7 +548,20 @@ class _BNApplyFn(torch.autograd.Function):
         # (grad mode is off inside Function.forward: whether a backward will run is needs_input_grad)
         want_mask = relu and any(ctx.needs_input_grad) and C % 8 == 0
         mask = torch.empty(M * C // 8, device=x.device, dtype=torch.uint8) if want_mask else None
-        if res_stride > 1:
+        if (defer and relu and res_mode and res_stride == 1 and C % 8 == 0 and C <= 512 and M * C < (1 << 30) and
+                x.is_cuda and x.dtype == torch.bfloat16 and res.dtype == torch.bfloat16 and x.is_contiguous() and
+                res.is_contiguous()):
+            # the launch is deferred to the first consumer of y (lazy.DeferredBlockOut); everything else - saved
+            # tensors, mask, _dtm_bnout, backward - is as below (these shapes always have the bitmask form)
+            try:
+                y._dtm_defer = _DeferState(x, ss, res, res_ss, mask, res_mode)
+            except Exception:
+                defer = False
+        else:
+            defer = False
+        if defer:
+            pass
+        elif res_stride > 1:
             N, Ho, Wo, _ = x.shape
             _check(L.dtm_bn_apply_res_strided(_lib.ptr(x), _lib.ptr(ss), _lib.ptr(res), _lib.ptr(y), _lib.ptr(mask), N,
                                               Ho, Wo, C, res.shape[1], res.shape[2], res_stride, int(relu),
@@ -592,7 +650,7 @@ class _BNApplyFn(torch.autograd.Function):
             full = torch.zeros(ctx.res_shape, device=dres.device, dtype=dres.dtype)
             full[:, ::st, ::st, :] = dres
             dres = full
-        return dx, sx, dres, sr, None, None, None, None
+        return dx, sx, dres, sr, None, None, None, None, None
 
 
 class _StemConvBNFn(torch.autograd.Function):
@@ -713,9 +771,17 @@ def _stem_eligible(x, w, stride, g):
             g.pad_h >= 0 and g.dilation == 1)
 
 
-def bn_apply(raw, ss, relu, residual=None, unscaled=False):
+def bn_apply(raw, ss, relu, residual=None, unscaled=False, defer=False):
     """y = relu?(raw*scale+shift + residual); residual may be a tensor, a LazyBN (BN'd shortcut) or a
-    Subsampled block input (strided identity shortcut).  ``unscaled``: raw's LazyBN.unscaled."""
+    Subsampled block input (strided identity shortcut).  ``unscaled``: raw's LazyBN.unscaled.
+    ``defer``: return a ``DeferredBlockOut`` (the launch left to the first consumer) where the op has that form."""
+    if defer:
+        y = _bn_apply(raw, ss, relu, residual, unscaled, True)
+        return DeferredBlockOut(y) if getattr(y, "_dtm_defer", None) is not None else y
+    return _bn_apply(raw, ss, relu, residual, unscaled, False)
+
+
+def _bn_apply(raw, ss, relu, residual, unscaled, defer):
     ux = 1 if unscaled else 0
     if residual is None:
         return _BNApplyFn.apply(raw, ss, None, None, bool(relu), None, 1, ux)
@@ -731,10 +797,10 @@ def bn_apply(raw, ss, relu, residual=None, unscaled=False):
             residual = residual.materialize()
         else:
             return _BNApplyFn.apply(raw, ss, residual.raw, residual.ss, bool(relu), None, 1,
-                                    ux | (2 if residual.unscaled else 0))
+                                    ux | (2 if residual.unscaled else 0), defer)
     res = residual.to(torch.bfloat16).contiguous()
     slot = _slot_register(res) if res is residual else None
-    return _BNApplyFn.apply(raw, ss, res, None, bool(relu), slot, 1, ux)
+    return _BNApplyFn.apply(raw, ss, res, None, bool(relu), slot, 1, ux, defer)
 
 
 def bn_apply_nograd(raw, ss):
@@ -1061,6 +1127,13 @@ def conv_bn(x, w, bn, stride, padding, training, relu):
     in_ss = None
     in_unscaled = False
     x_mat = None
+    if isinstance(x, DeferredBlockOut):
+        # an unfilled block output (a contiguous bf16 tensor: no copy below): a training conv+BN of its own forms it in
+        # its forward where the kernel takes the shape (_ConvBNFn.forward); every other case - a sibling group's merged
+        # forward included - gets it from the ordinary BN-apply here
+        if not (training and bn is not None and _SIBLINGS[0] is None and features.on("blockout_conv_fuse")):
+            x.materialize()
+        x = x.y
     if isinstance(x, LazyBN):
         mode = _prologue_mode(tuple(x.shape), tuple(w.shape), stride) if x.relu else "apply"
         if mode == "apply" or x.ss.shape[1] % 8 != 0:

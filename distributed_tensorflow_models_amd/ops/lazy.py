@@ -35,10 +35,12 @@ class LazyBN:
     def dim(self):
         return self.raw.dim()
 
-    def materialize(self, residual=None, residual_act=None):
+    def materialize(self, residual=None, residual_act=None, defer=False):
+        """defer: the caller's next op is an eligible conv - return a ``DeferredBlockOut`` where the BN-apply can be
+        merged into it (else the tensor as usual)."""
         from .fused import bn_apply
         relu = self.relu if residual is None else residual_act == "relu"
-        return bn_apply(self.raw, self.ss, relu, residual, unscaled=self.unscaled)
+        return bn_apply(self.raw, self.ss, relu, residual, unscaled=self.unscaled, defer=defer)
 
 
 class Subsampled:
@@ -66,5 +68,48 @@ class Subsampled:
         return F.max_pool(self.src, 1, self.stride, "VALID")
 
 
+class DeferredBlockOut:
+    """A bottleneck unit's output y = relu(bn(raw) + residual) whose BN-apply launch is deferred to its first
+    consumer.  ``y`` already is the output of the BN-apply's autograd node (ops.fused ``_BNApplyFn``: saved tensors,
+    ReLU bitmask and backward as usual), only its storage is not filled yet; the launch parameters are ``y._dtm_defer``
+    (ops.fused ``_DeferState``).  The next unit's 1x1 conv1 forms y while it stages its operand and stores it as a
+    side output (``_ConvBNFn`` forward, feature ``blockout_conv_fuse``); any other first consumer gets it from
+    ``materialize``, which runs the ordinary BN-apply kernel.  Exactly one of the two launches fills y, and ``y``
+    leaves this object only filled (``as_tensor``)."""
+
+    __slots__ = ("y",)
+
+    def __init__(self, y):
+        self.y = y
+
+    @property
+    def shape(self):
+        return self.y.shape
+
+    @property
+    def is_cuda(self):
+        return self.y.is_cuda
+
+    @property
+    def dtype(self):
+        return self.y.dtype
+
+    @property
+    def device(self):
+        return self.y.device
+
+    def dim(self):
+        return self.y.dim()
+
+    @property
+    def filled(self):
+        return getattr(self.y, "_dtm_defer", None) is None
+
+    def materialize(self):
+        from .fused import blockout_fill
+        blockout_fill(self.y)
+        return self.y
+
+
 def as_tensor(x):
-    return x.materialize() if isinstance(x, (LazyBN, Subsampled)) else x
+    return x.materialize() if isinstance(x, (LazyBN, Subsampled, DeferredBlockOut)) else x

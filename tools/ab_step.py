@@ -17,7 +17,8 @@ dgrp (0/1: strided-dgrad parity classes as one grouped launch), atile (tile id o
 activation-backward epilogue, -1 = policy), rsv (CUs reserved from the compute grids' sizing), lpt (0/1: grouped
 parity classes in descending tap count), dtile (0/1: grouped strided-dgrad tile chosen for the whole grouped grid),
 stile (0/1: merged-head convs on the pipelined 128x128 tile), fdir (0/1: one-block BN finalize when one row
-chunk covers every statistics row), hog (blocks:ms - a CU-occupying copy kernel on another
+chunk covers every statistics row), bo (mode[:nt] - the block-output prologue of the identity units' conv1, -1 policy /
+0 declined / 1 every eligible launch / 2, 3 only its 128x64 / 64x128 tile; nt 0/1 = non-temporal loads of its two streamed inputs), hog (blocks:ms - a CU-occupying copy kernel on another
 stream from every backward start, standing in for RCCL channels), wtile[:occ] (wgrad tile id / blocks-per-CU target),
 prologue (auto | fused | mat | apply: ops/fused.py PROLOGUE_MODE), red (target_blocks:max_chunks[:direct_max] of the
 partial-sum reductions), off (name+name: fused-path features of ops/features.py switched off, e.g.
@@ -90,6 +91,8 @@ def apply(cfg):
     L.dtm_conv_set_dec_tile(int(cfg.get("dtile", "1")))
     L.dtm_conv_set_split_tile(int(cfg.get("stile", "1")))
     L.dtm_set_fin_direct(int(cfg.get("fdir", "1")))
+    bo = cfg.get("bo", "-1:1").split(":")
+    L.dtm_conv_set_blockout(int(bo[0]), int(bo[1]) if len(bo) > 1 else 1)
     HOG[0] = cfg.get("hog")
     sc = cfg.get("sc", "5:4096").split(":")
     L.dtm_set_sc_policy(int(sc[0]), int(sc[1]))

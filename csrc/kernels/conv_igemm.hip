@@ -2905,6 +2905,13 @@ struct TileCfg {
   int id, PT, NWP;
 };
 static int g_tile_env = -2;
+// what ran last (read-only, for tests: dtm_conv_last_tiles): the tile id of the last conv_nt launch (forward / dgrad;
+// the last class of an ungrouped strided dgrad) and of the last weight gradient (20 = the direct 3x3 kernel); -1 = none
+static int g_last_nt_tile = -1, g_last_wgrad_tile = -1;
+DTM_API void dtm_conv_last_tiles(int* nt, int* wgrad) {
+  if (nt) *nt = g_last_nt_tile;
+  if (wgrad) *wgrad = g_last_wgrad_tile;
+}
 static int device_cus();
 static int g_policy2 = 1;  // A/B knob: the v2 shape-policy rules (dtm_conv_set_policy2)
 DTM_API void dtm_conv_set_policy2(int on) { g_policy2 = on; }
@@ -3030,6 +3037,8 @@ static TileCfg pick_tile_impl(const ConvNTArgs& a, bool stats) {
 
 // merged-sibling forwards (split store; no prologue, stride-1 1x1): the tiles conv_fwd_impl lets through
 static void dispatch_split(const ConvNTArgs& a, const TileCfg& t, hipStream_t st) {
+  const int id = t.id;
+  g_last_nt_tile = (id == 3 || id == 4 || id == 21 || id == 24 || id == 26 || id == 32 || id == 40 || id == 41) ? id : 0;
   if (t.id == 3) launch_nt<128, 64, 32, 64, 1, 1, true>(a, st);
   else if (t.id == 4) launch_nt<64, 128, 32, 64, 1, 1, true>(a, st);
   else if (t.id == 21) launch_pipe<128, 128, 2, 1, 2, true>(a, st);
@@ -3072,6 +3081,9 @@ static void dispatch_ud(const ConvNTArgs& a, const TileCfg& t, hipStream_t st) {
 DTM_API void dtm_conv_set_tile(int id) { g_tile_env = id; }
 
 static void dispatch_nt(const ConvNTArgs& a, int ud, const TileCfg& t, hipStream_t st) {
+  // (a split launch: dispatch_split records what it runs; the persistent / direct kernels exist for UD = 1 only,
+  // dispatch_ud<2> runs tile 0 in their place)
+  g_last_nt_tile = (ud != 1 && (t.id == 30 || t.id == 31 || t.id == 33 || t.id == 60)) ? 0 : t.id;
   if (ud == 1) dispatch_ud<1>(a, t, st);
   else dispatch_ud<2>(a, t, st);
 }
@@ -3096,6 +3108,7 @@ struct BlockOut {
 };
 constexpr int DTM_DECLINED = 1;  // not an error: the fused form does not apply to this launch, nothing was launched
 static void launch_blockout(const ConvNTArgs& a, int tile, hipStream_t st) {
+  g_last_nt_tile = tile == 3 ? 3 : 4;
   // the tiles of launch_nt_act's forward-with-statistics variant, held at its 3 waves / SIMD
   if (tile == 3) {
     if (g_blockout_nt) launch_nt<128, 64, 32, 64, 1, 1, false, 3, 4, 2>(a, st);
@@ -3517,6 +3530,7 @@ static int wgrad_direct_k(ConvWgradArgs& a, const ConvDesc* d, int num_cus, hipS
 static int g_wgrad_direct_kt = 64;  // dW rows per block when K % 64 == 0 (A/B: dtm_conv_set_wgrad_direct_kt)
 DTM_API void dtm_conv_set_wgrad_direct_kt(int kt) { g_wgrad_direct_kt = kt; }
 static int wgrad_direct(ConvWgradArgs& a, const ConvDesc* d, int num_cus, hipStream_t st, float* dw) {
+  g_last_wgrad_tile = 20;
   const bool k64 = d->K % 64 == 0 && g_wgrad_direct_kt == 64;
   if (d->C == 32) return k64 ? wgrad_direct_k<32, 64>(a, d, num_cus, st, dw) : wgrad_direct_k<32, 32>(a, d, num_cus, st, dw);
   return k64 ? wgrad_direct_k<64, 64>(a, d, num_cus, st, dw) : wgrad_direct_k<64, 32>(a, d, num_cus, st, dw);
@@ -3620,6 +3634,7 @@ static int conv_wgrad_impl(const void* x, const void* dy, float* dw, const float
   if (wenv == -1 && g_stem_bna && bn && !in_scale && d->K > 32 && d->K <= 64 && a.Kg <= 256) wt = 15;
   if (wt == 12 && g_tile_pp && wenv == -1) wt = 13;  // (the ping-pong form of the 256x256 tile, A/B knob dtm_conv_set_pp)
   if (wt != 0 && wt != 1 && wt != 6 && wt != 7 && wt != 8 && !(wt >= 10 && wt <= 16)) wt = 0;
+  g_last_wgrad_tile = wt;
   {
     static int log = -1;  // DTM_TILE_LOG=1: one stderr line per weight-gradient decision too
     if (log < 0) {

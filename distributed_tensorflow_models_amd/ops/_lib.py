@@ -80,6 +80,7 @@ _SIGS = {
     "dtm_maxpool_bnrelu_bwd": (_I, [_P, _P, _P, _P, _P, _P, ctypes.POINTER(PoolArgs), _I, _P]),
     "dtm_conv_set_tile": (None, [_I]),
     "dtm_conv_set_wgrad_tile": (None, [_I, _I]),
+    "dtm_conv_last_tiles": (None, [ctypes.POINTER(_I), ctypes.POINTER(_I)]),
     "dtm_loss_combine": (_I, [_P, _I, _I, _P, _P, _P]),
     "dtm_scale_rows_pad": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _P]),
     "dtm_conv_set_wgrad_k64": (None, [_I]),

@@ -3649,7 +3649,7 @@ static int conv_wgrad_impl(const void* x, const void* dy, float* dw, const float
   const bool k64w = wt == 1 || wt == 7 || wt == 8 || wt == 11 || (wt >= 14 && wt <= 16);  // 64-row tiles
   const int MT = wt == 6 ? 32 : (k64w ? 64 : (big ? 256 : 128)), NT = (big || (k64w && wt != 1)) ? 256 : 128;
   if (big) occ = ((wenv == 12 || wenv == 13) && g_wgrad_occ != 4) ? g_wgrad_occ : 1;
-  if (wt >= 14 && wt <= 16) occ = (wenv >= 14 && g_wgrad_occ != 4) ? g_wgrad_occ : 1;  // (the BNA tiles: 1 block per CU)  // (sweeps: WTILES=12:<occ>)
+  if (wt >= 14 && wt <= 16) occ = (wenv >= 14 && g_wgrad_occ != 4) ? g_wgrad_occ : 1;  // (the BNA tiles: 1 block per CU)
   long tiles = (long)((a.Kg + NT - 1) / NT) * ((a.K + MT - 1) / MT);
   // register-staged tiles: 3 blocks' worth of splits per CU (sweeps: WTILES=<1|6|0>:<occ>, occ != 4)
   const int rs_occ = (wenv >= 0 && g_wgrad_occ != 4) ? g_wgrad_occ : 3;

@@ -29,7 +29,7 @@
 #include <float.h>
 #include <limits.h>
 
-#include "common.h"
+#include "chunk_walk.h"
 
 namespace dtm {
 
@@ -43,39 +43,7 @@ enum : unsigned {
   MF_VALID = 1u, MF_FINITE = 2u, MF_TOP1 = 4u, MF_TOPK = 8u, MF_ARGMAX = 16u,
 };
 
-// f(c, v) for every element of the row x[0..C), each lane its own share in increasing c
-template <bool BF16, typename F>
-__device__ __forceinline__ void row_visit(const void* xrow, int C, int lane, F f) {
-  if (BF16) {
-    const bf16_t* x = (const bf16_t*)xrow;
-    int head = (int)(((16u - (unsigned)((uintptr_t)x & 15u)) & 15u) >> 1);
-    head = head < C ? head : C;
-    const int nvec = (C - head) >> 3, tail0 = head + (nvec << 3);
-    if (lane < head) f(lane, bf2f(x[lane]));
-    const short8* xv = (const short8*)(x + head);
-    for (int i = lane; i < nvec; i += 64) {
-      const short8 w = xv[i];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) f(head + (i << 3) + e, bf2f((bf16_t)w[e]));
-    }
-    if (tail0 + lane < C) f(tail0 + lane, bf2f(x[tail0 + lane]));  // (tail < 8 elements)
-  } else {
-    const float* x = (const float*)xrow;
-    int head = (int)(((16u - (unsigned)((uintptr_t)x & 15u)) & 15u) >> 2);
-    head = head < C ? head : C;
-    const int nvec = (C - head) >> 2, tail0 = head + (nvec << 2);
-    if (lane < head) f(lane, x[lane]);
-    const f32x4* xv = (const f32x4*)(x + head);
-    for (int i = lane; i < nvec; i += 64) {
-      const f32x4 w = xv[i];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) f(head + (i << 2) + e, w[e]);
-    }
-    if (tail0 + lane < C) f(tail0 + lane, x[tail0 + lane]);  // (tail < 4 elements)
-  }
-}
-
-template <bool BF16>
+template <typename T>
 __global__ __launch_bounds__(256) void eval_metrics_rows_kernel(const void* __restrict__ logits,
                                                                 const void* __restrict__ labels, int lab64, int B,
                                                                 int C, int k, int confusion,
@@ -89,14 +57,13 @@ __global__ __launch_bounds__(256) void eval_metrics_rows_kernel(const void* __re
     if (lane == 0) { flags[row] = 0u; rowloss[row] = 0.0; }
     return;
   }
-  const void* xrow = BF16 ? (const void*)((const bf16_t*)logits + (long)row * C)
-                          : (const void*)((const float*)logits + (long)row * C);
-  const float xt = BF16 ? bf2f(((const bf16_t*)xrow)[t]) : ((const float*)xrow)[t];
+  const T* xrow = (const T*)logits + (long)row * C;
+  const float xt = elem_f32(xrow[t]);
 
   float m = -INFINITY;
   int idx = INT_MAX, greater = 0;
   bool fin = true;
-  row_visit<BF16>(xrow, C, lane, [&](int c, float v) {
+  visit_row<64>(xrow, C, lane, [&](int c, float v) {  // each lane its own share of the row, in increasing c
     fin = fin && fabsf(v) <= FLT_MAX;
     greater += v > xt ? 1 : 0;
     if (v > m) { m = v; idx = c; }  // strictly greater, c increasing: the lane's lowest index of its maximum
@@ -115,7 +82,7 @@ __global__ __launch_bounds__(256) void eval_metrics_rows_kernel(const void* __re
   double loss = 0.0;
   if (finite_row) {  // (wave-uniform)
     float s = 0.f;
-    row_visit<BF16>(xrow, C, lane, [&](int, float v) { s += expf(v - m); });
+    visit_row<64>(xrow, C, lane, [&](int, float v) { s += expf(v - m); });
     s = warp_sum(s);  // fixed order: the lane's elements in index order, then the xor butterfly
     loss = (double)logf(s) + ((double)m - (double)xt);
   }
@@ -134,12 +101,6 @@ __global__ __launch_bounds__(256) void eval_metrics_rows_kernel(const void* __re
   }
 }
 
-__device__ __forceinline__ double metrics_wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(METRICS_FIN_THREADS) void eval_metrics_finalize_kernel(
     const double* __restrict__ rowloss, const unsigned* __restrict__ flags, int B,
     unsigned long long* __restrict__ rec) {
@@ -155,7 +116,7 @@ __global__ __launch_bounds__(METRICS_FIN_THREADS) void eval_metrics_finalize_ker
 #pragma unroll
     for (int b = 0; b < 5; ++b) cnt[b] += (int)((f >> b) & 1u);
   }
-  loss = metrics_wave_sum_f64(loss);
+  loss = wave_sum_f64(loss);
 #pragma unroll
   for (int b = 0; b < 5; ++b) {
 #pragma unroll
@@ -212,10 +173,10 @@ DTM_API int dtm_eval_metrics(const void* logits, int dtype, const void* labels, 
   hipStream_t st = (hipStream_t)stream;
   const unsigned grid = (unsigned)((B + 3) / 4);
   if (dtype == 1)
-    hipLaunchKernelGGL(eval_metrics_rows_kernel<true>, dim3(grid), dim3(256), 0, st, logits, labels, lab64, B, C, k,
+    hipLaunchKernelGGL(eval_metrics_rows_kernel<bf16_t>, dim3(grid), dim3(256), 0, st, logits, labels, lab64, B, C, k,
                        confusion, (unsigned long long*)rec, (double*)rowloss, (unsigned*)flags);
   else
-    hipLaunchKernelGGL(eval_metrics_rows_kernel<false>, dim3(grid), dim3(256), 0, st, logits, labels, lab64, B, C, k,
+    hipLaunchKernelGGL(eval_metrics_rows_kernel<float>, dim3(grid), dim3(256), 0, st, logits, labels, lab64, B, C, k,
                        confusion, (unsigned long long*)rec, (double*)rowloss, (unsigned*)flags);
   hipLaunchKernelGGL(eval_metrics_finalize_kernel, dim3(1), dim3(METRICS_FIN_THREADS), 0, st,
                      (const double*)rowloss, (const unsigned*)flags, B, (unsigned long long*)rec);

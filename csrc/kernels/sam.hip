@@ -19,7 +19,8 @@
 // Bytes per element with the bf16 copy: norm 4 (ASAM 8); perturb 8 read + 14 written; restore 4 read + 6 written.
 // 16-byte accesses (8 for the bf16 copy) where all arrays a launch touches reach a 16-byte boundary together, with a
 // scalar head and tail; coalesced 4-byte accesses otherwise (gradients are views into the flat buffer at any offset).
-#include "common.h"
+// The walk and the fixed-order sums are chunk_walk.h's.
+#include "chunk_walk.h"
 
 namespace dtm {
 
@@ -30,31 +31,8 @@ struct SamTensor {
   bf16_t* pcopy;  // optional bf16 compute copy
   long n;
 };
-struct SamChunk {
-  int t;
-  int pad;
-  long start;
-};
-struct SamMeta {  // per tensor: its rows of the chunk table
-  int chunk0, nchunks;
-};
 constexpr int SAM_CHUNK = 8192;
 constexpr int SAM_FIN_THREADS = 1024;
-
-__device__ __forceinline__ double sam_wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-__device__ __forceinline__ int sam_len(long n, long start) {
-  const long rem = n - start;
-  return (int)(rem < (long)SAM_CHUNK ? (rem > 0 ? rem : 0) : (long)SAM_CHUNK);
-}
-// elements in front of the first 16-byte boundary
-__device__ __forceinline__ int sam_head16(const void* a) {
-  return (int)(((16u - (unsigned)((uintptr_t)a & 15u)) & 15u) >> 2);
-}
 
 template <bool ADAPTIVE>
 __device__ __forceinline__ double sam_term(float p, float g) {
@@ -65,61 +43,47 @@ __device__ __forceinline__ double sam_term(float p, float g) {
 
 template <bool ADAPTIVE>
 __global__ __launch_bounds__(256) void sam_norm_kernel(const SamTensor* __restrict__ tens,
-                                                       const SamChunk* __restrict__ chunks, double* __restrict__ recs) {
-  __shared__ double red[4];
+                                                       const ChunkRow* __restrict__ chunks, double* __restrict__ recs) {
   const int tid = threadIdx.x;
-  const SamChunk c = chunks[blockIdx.x];
+  const ChunkRow c = chunks[blockIdx.x];
   const SamTensor t = tens[c.t];
-  double a = 0.0;
+  double a[1] = {0.0};
   if (t.g) {
-    const int len = sam_len(t.n, c.start);
-    const float* pp = t.p + c.start;
+    const float* pp = t.p + c.start;  // (read by ASAM only)
     const float* gp = t.g + c.start;
-    if (!ADAPTIVE || (((uintptr_t)pp ^ (uintptr_t)gp) & 15u) == 0) {
-      int head = sam_head16(gp);
-      head = head < len ? head : len;
-      const int nvec = (len - head) >> 2, tail0 = head + (nvec << 2);
-      if (tid < head) a += sam_term<ADAPTIVE>(ADAPTIVE ? pp[tid] : 0.f, gp[tid]);
-      const f32x4* pv = (const f32x4*)(pp + head);
-      const f32x4* gv = (const f32x4*)(gp + head);
-      for (int i = tid; i < nvec; i += 256) {
-        const f32x4 gw = gv[i];
-        f32x4 pw = {0.f, 0.f, 0.f, 0.f};
-        if constexpr (ADAPTIVE) pw = pv[i];
+    const WalkPlan w =
+        walk_plan(4, (uintptr_t)gp, chunk_len(t.n, c.start, SAM_CHUNK), !ADAPTIVE || same16(gp, pp));
+    const f32x4* pv = (const f32x4*)(pp + w.head);
+    const f32x4* gv = (const f32x4*)(gp + w.head);
+    walk<256, 4>(
+        w, tid, [&](int i) { a[0] += sam_term<ADAPTIVE>(ADAPTIVE ? pp[i] : 0.f, gp[i]); },
+        [&](int i, int) {
+          const f32x4 gw = gv[i];
+          f32x4 pw = {0.f, 0.f, 0.f, 0.f};
+          if constexpr (ADAPTIVE) pw = pv[i];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) a += sam_term<ADAPTIVE>(pw[e], gw[e]);
-      }
-      if (tail0 + tid < len) a += sam_term<ADAPTIVE>(ADAPTIVE ? pp[tail0 + tid] : 0.f, gp[tail0 + tid]);
-    } else {
-      for (int i = tid; i < len; i += 256) a += sam_term<ADAPTIVE>(pp[i], gp[i]);
-    }
+          for (int e = 0; e < 4; ++e) a[0] += sam_term<ADAPTIVE>(pw[e], gw[e]);
+        });
   }
-  // fixed order: xor butterfly over each wave, then the four waves in LDS
-  a = sam_wave_sum_f64(a);
-  if ((tid & 63) == 0) red[tid >> 6] = a;
-  __syncthreads();
-  if (tid == 0) recs[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+  block_sum_f64(a, tid);
+  if (tid == 0) recs[blockIdx.x] = a[0];
 }
 
-__global__ __launch_bounds__(SAM_FIN_THREADS) void sam_finalize_kernel(const SamMeta* __restrict__ meta, int ntens,
+__global__ __launch_bounds__(SAM_FIN_THREADS) void sam_finalize_kernel(const ChunkSpan* __restrict__ meta, int ntens,
                                                                        const double* __restrict__ recs,
                                                                        double* __restrict__ tsum, double rho,
                                                                        float* __restrict__ out) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  double s[1];
   for (int t = wv; t < ntens; t += SAM_FIN_THREADS / 64) {  // one wave per tensor
-    const SamMeta m = meta[t];
-    double s = 0.0;
-    for (int j = lane; j < m.nchunks; j += 64) s += recs[m.chunk0 + j];
-    s = sam_wave_sum_f64(s);
-    if (lane == 0) tsum[t] = s;
+    record_sum(recs, meta[t], lane, s);
+    if (lane == 0) tsum[t] = s[0];
   }
   __syncthreads();
-  if (wv == 0) {
-    double s = 0.0;
-    for (int t = lane; t < ntens; t += 64) s += tsum[t];
-    s = sam_wave_sum_f64(s);
+  if (wv == 0) {  // the per-tensor sums the same way, in tensor order
+    record_sum((const double*)tsum, ChunkSpan{0, ntens}, lane, s);
     if (lane == 0) {
-      const double nrm = sqrt(s);
+      const double nrm = sqrt(s[0]);
       out[0] = (float)nrm;
       out[1] = (float)(rho / (nrm + 1e-12));
     }
@@ -144,12 +108,12 @@ __device__ __forceinline__ float sam_phat(float p, float g, float scale) {
 
 template <bool ADAPTIVE>
 __global__ __launch_bounds__(256) void sam_perturb_kernel(const SamTensor* __restrict__ tens,
-                                                          const SamChunk* __restrict__ chunks,
+                                                          const ChunkRow* __restrict__ chunks,
                                                           const float* __restrict__ rec) {
   const int tid = threadIdx.x;
-  const SamChunk c = chunks[blockIdx.x];
+  const ChunkRow c = chunks[blockIdx.x];
   const SamTensor t = tens[c.t];
-  const int len = sam_len(t.n, c.start);
+  const int len = chunk_len(t.n, c.start, SAM_CHUNK);
   float* pp = t.p + c.start;
   float* bp = t.backup + c.start;
   if (!t.g) {  // backup-only row: a bit copy
@@ -162,76 +126,60 @@ __global__ __launch_bounds__(256) void sam_perturb_kernel(const SamTensor* __res
   float* gp = t.g + c.start;
   bf16_t* cp = t.pcopy ? t.pcopy + c.start : nullptr;
 
-  auto scalar = [&](int i) {
-    const float p = pp[i];
-    const float r = sam_phat<ADAPTIVE>(p, gp[i], scale);
-    ((uint32_t*)bp)[i] = __float_as_uint(p);
-    pp[i] = r;
-    if (cp) cp[i] = f2bf(r);
-    gp[i] = 0.f;
-  };
-
-  const uintptr_t pa = (uintptr_t)pp;
-  const uintptr_t off = (pa ^ (uintptr_t)gp) | (pa ^ (uintptr_t)bp);
-  const int head16 = sam_head16(pp);
-  if ((off & 15u) == 0 && (!cp || ((uintptr_t)(cp + head16) & 7u) == 0)) {
-    const int head = head16 < len ? head16 : len;
-    const int nvec = (len - head) >> 2, tail0 = head + (nvec << 2);
-    if (tid < head) scalar(tid);
-    f32x4* pv = (f32x4*)(pp + head);
-    f32x4* gv = (f32x4*)(gp + head);
-    uint4* bv = (uint4*)(bp + head);
-    for (int i = tid; i < nvec; i += 256) {
-      const f32x4 pw = pv[i], gw = gv[i];
-      f32x4 rw;
+  const WalkPlan w = walk_plan(4, (uintptr_t)pp, len, same16(pp, gp, bp) && copy8_ok(cp, (uintptr_t)pp));
+  f32x4* pv = (f32x4*)(pp + w.head);
+  f32x4* gv = (f32x4*)(gp + w.head);
+  uint4* bv = (uint4*)(bp + w.head);
+  walk<256, 4>(
+      w, tid,
+      [&](int i) {
+        const float p = pp[i];
+        const float r = sam_phat<ADAPTIVE>(p, gp[i], scale);
+        ((uint32_t*)bp)[i] = __float_as_uint(p);
+        pp[i] = r;
+        if (cp) cp[i] = f2bf(r);
+        gp[i] = 0.f;
+      },
+      [&](int i, int) {
+        const f32x4 pw = pv[i], gw = gv[i];
+        f32x4 rw;
 #pragma unroll
-      for (int e = 0; e < 4; ++e) rw[e] = sam_phat<ADAPTIVE>(pw[e], gw[e], scale);
-      bv[i] = make_uint4(__float_as_uint(pw[0]), __float_as_uint(pw[1]), __float_as_uint(pw[2]),
-                         __float_as_uint(pw[3]));
-      pv[i] = rw;
-      if (cp) ((uint2*)(cp + head))[i] = make_uint2(pack2bf(rw[0], rw[1]), pack2bf(rw[2], rw[3]));
-      gv[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-    if (tail0 + tid < len) scalar(tail0 + tid);
-  } else {
-    for (int i = tid; i < len; i += 256) scalar(i);
-  }
+        for (int e = 0; e < 4; ++e) rw[e] = sam_phat<ADAPTIVE>(pw[e], gw[e], scale);
+        bv[i] = make_uint4(__float_as_uint(pw[0]), __float_as_uint(pw[1]), __float_as_uint(pw[2]),
+                           __float_as_uint(pw[3]));
+        pv[i] = rw;
+        if (cp) store_bf16x4(cp + w.head, i, rw);
+        gv[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+      });
 }
 
 __global__ __launch_bounds__(256) void sam_restore_kernel(const SamTensor* __restrict__ tens,
-                                                          const SamChunk* __restrict__ chunks) {
+                                                          const ChunkRow* __restrict__ chunks) {
   const int tid = threadIdx.x;
-  const SamChunk c = chunks[blockIdx.x];
+  const ChunkRow c = chunks[blockIdx.x];
   const SamTensor t = tens[c.t];
-  const int len = sam_len(t.n, c.start);
   uint32_t* pp = (uint32_t*)(t.p + c.start);
   const uint32_t* bp = (const uint32_t*)(t.backup + c.start);
   bf16_t* cp = (t.g && t.pcopy) ? t.pcopy + c.start : nullptr;
 
-  auto scalar = [&](int i) {
-    const uint32_t b = bp[i];
-    pp[i] = b;
-    if (cp) cp[i] = f2bf(__uint_as_float(b));
-  };
-
-  const int head16 = sam_head16(pp);
-  if (((((uintptr_t)pp) ^ (uintptr_t)bp) & 15u) == 0 && (!cp || ((uintptr_t)(cp + head16) & 7u) == 0)) {
-    const int head = head16 < len ? head16 : len;
-    const int nvec = (len - head) >> 2, tail0 = head + (nvec << 2);
-    if (tid < head) scalar(tid);
-    uint4* pv = (uint4*)(pp + head);
-    const uint4* bv = (const uint4*)(bp + head);
-    for (int i = tid; i < nvec; i += 256) {
-      const uint4 b = bv[i];
-      pv[i] = b;
-      if (cp)
-        ((uint2*)(cp + head))[i] = make_uint2(pack2bf(__uint_as_float(b.x), __uint_as_float(b.y)),
-                                              pack2bf(__uint_as_float(b.z), __uint_as_float(b.w)));
-    }
-    if (tail0 + tid < len) scalar(tail0 + tid);
-  } else {
-    for (int i = tid; i < len; i += 256) scalar(i);
-  }
+  const WalkPlan w = walk_plan(4, (uintptr_t)pp, chunk_len(t.n, c.start, SAM_CHUNK),
+                               same16(pp, bp) && copy8_ok(cp, (uintptr_t)pp));
+  uint4* pv = (uint4*)(pp + w.head);
+  const uint4* bv = (const uint4*)(bp + w.head);
+  walk<256, 4>(
+      w, tid,
+      [&](int i) {
+        const uint32_t b = bp[i];
+        pp[i] = b;
+        if (cp) cp[i] = f2bf(__uint_as_float(b));
+      },
+      [&](int i, int) {
+        const uint4 b = bv[i];
+        pv[i] = b;
+        if (cp)
+          store_bf16x4(cp + w.head, i,
+                       f32x4{__uint_as_float(b.x), __uint_as_float(b.y), __uint_as_float(b.z), __uint_as_float(b.w)});
+      });
 }
 
 }  // namespace dtm
@@ -239,8 +187,8 @@ using namespace dtm;
 
 DTM_API int dtm_sam_chunk_size() { return SAM_CHUNK; }
 DTM_API int dtm_sam_tensor_bytes() { return (int)sizeof(SamTensor); }
-DTM_API int dtm_sam_chunk_bytes() { return (int)sizeof(SamChunk); }
-DTM_API int dtm_sam_meta_bytes() { return (int)sizeof(SamMeta); }
+DTM_API int dtm_sam_chunk_bytes() { return (int)sizeof(ChunkRow); }
+DTM_API int dtm_sam_meta_bytes() { return (int)sizeof(ChunkSpan); }
 // scratch: one fp64 record per chunk row, then one fp64 sum per tensor
 DTM_API long dtm_sam_scratch_bytes(int num_chunks, int ntens) {
   return 8L * ((long)(num_chunks > 0 ? num_chunks : 0) + (long)(ntens > 0 ? ntens : 0));
@@ -256,13 +204,13 @@ DTM_API int dtm_sam_perturb(const void* tensors_dev, const void* chunks_dev, int
   if (!tensors_dev || !chunks_dev || !meta_dev || !scratch || !out) return -1;
   hipStream_t st = (hipStream_t)stream;
   const SamTensor* tens = (const SamTensor*)tensors_dev;
-  const SamChunk* chunks = (const SamChunk*)chunks_dev;
+  const ChunkRow* chunks = (const ChunkRow*)chunks_dev;
   double* recs = (double*)scratch;
   double* tsum = recs + num_chunks;
   const dim3 grid((unsigned)num_chunks), block(256);
   if (adaptive) hipLaunchKernelGGL(sam_norm_kernel<true>, grid, block, 0, st, tens, chunks, recs);
   else hipLaunchKernelGGL(sam_norm_kernel<false>, grid, block, 0, st, tens, chunks, recs);
-  hipLaunchKernelGGL(sam_finalize_kernel, dim3(1), dim3(SAM_FIN_THREADS), 0, st, (const SamMeta*)meta_dev, ntens,
+  hipLaunchKernelGGL(sam_finalize_kernel, dim3(1), dim3(SAM_FIN_THREADS), 0, st, (const ChunkSpan*)meta_dev, ntens,
                      (const double*)recs, tsum, rho, (float*)out);
   if (adaptive) hipLaunchKernelGGL(sam_perturb_kernel<true>, grid, block, 0, st, tens, chunks, (const float*)out);
   else hipLaunchKernelGGL(sam_perturb_kernel<false>, grid, block, 0, st, tens, chunks, (const float*)out);
@@ -276,6 +224,6 @@ DTM_API int dtm_sam_restore(const void* tensors_dev, const void* chunks_dev, int
   if (num_chunks <= 0) return -3;
   if (!tensors_dev || !chunks_dev) return -1;
   hipLaunchKernelGGL(sam_restore_kernel, dim3((unsigned)num_chunks), dim3(256), 0, (hipStream_t)stream,
-                     (const SamTensor*)tensors_dev, (const SamChunk*)chunks_dev);
+                     (const SamTensor*)tensors_dev, (const ChunkRow*)chunks_dev);
   return 0;
 }

@@ -16,7 +16,7 @@
 // output is bit-identical from run to run (independent of dtm_set_deterministic).
 #include <float.h>
 
-#include "common.h"
+#include "chunk_walk.h"
 
 namespace dtm {
 
@@ -31,11 +31,6 @@ struct StatsTensor {
   int bf16;              // 0: fp32 row, 1: bf16 row
   unsigned chunk0;       // this tensor's first row in the chunk table / the partial records
   unsigned nchunks;
-};
-struct StatsChunk {
-  int t;
-  int pad;
-  long start;
 };
 struct StatsPartial {  // one per chunk
   double sum, sumsq;
@@ -87,7 +82,7 @@ __device__ __forceinline__ void stats_add(StatsAcc& a, unsigned* hist, const dou
 }
 
 __global__ __launch_bounds__(256) void tensor_stats_kernel(const StatsTensor* __restrict__ tens,
-                                                           const StatsChunk* __restrict__ chunks,
+                                                           const ChunkRow* __restrict__ chunks,
                                                            const double* __restrict__ limits,
                                                            unsigned* __restrict__ bins,
                                                            StatsPartial* __restrict__ partials) {
@@ -97,7 +92,7 @@ __global__ __launch_bounds__(256) void tensor_stats_kernel(const StatsTensor* __
   __shared__ float rmn[256], rmx[256];
   __shared__ unsigned rz[256], rnf[256];
   const int tid = threadIdx.x;
-  const StatsChunk c = chunks[blockIdx.x];
+  const ChunkRow c = chunks[blockIdx.x];
   const StatsTensor t = tens[c.t];
   for (int i = tid; i < STATS_BUCKETS; i += 256) {
     lim[i] = limits[i];
@@ -105,38 +100,13 @@ __global__ __launch_bounds__(256) void tensor_stats_kernel(const StatsTensor* __
   }
   __syncthreads();
 
-  const long rem = (long)t.n - c.start;
-  const int len = (int)(rem < (long)STATS_CHUNK ? rem : (long)STATS_CHUNK);  // >= 1 (host-built table)
+  const int len = chunk_len((long)t.n, c.start, STATS_CHUNK);  // >= 1 (host-built table)
   StatsAcc a = {0.0, 0.0, INFINITY, -INFINITY, 0u, 0u};
   // 16-byte loads over the aligned body; a scalar head up to the first 16-byte boundary and a scalar tail
   // (tensors are slices of flat buffers: a chunk can start at any element)
-  if (t.bf16) {
-    const bf16_t* x = (const bf16_t*)t.x + c.start;
-    int head = (int)(((16u - (unsigned)((uintptr_t)x & 15u)) & 15u) >> 1);
-    head = head < len ? head : len;
-    const int nvec = (len - head) >> 3, tail0 = head + (nvec << 3);
-    if (tid < head) stats_add(a, hist, lim, bf2f(x[tid]), t.scale);
-    const short8* xv = (const short8*)(x + head);
-    for (int i = tid; i < nvec; i += 256) {
-      const short8 w = xv[i];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) stats_add(a, hist, lim, bf2f((bf16_t)w[e]), t.scale);
-    }
-    if (tail0 + tid < len) stats_add(a, hist, lim, bf2f(x[tail0 + tid]), t.scale);
-  } else {
-    const float* x = (const float*)t.x + c.start;
-    int head = (int)(((16u - (unsigned)((uintptr_t)x & 15u)) & 15u) >> 2);
-    head = head < len ? head : len;
-    const int nvec = (len - head) >> 2, tail0 = head + (nvec << 2);
-    if (tid < head) stats_add(a, hist, lim, x[tid], t.scale);
-    const f32x4* xv = (const f32x4*)(x + head);
-    for (int i = tid; i < nvec; i += 256) {
-      const f32x4 w = xv[i];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) stats_add(a, hist, lim, w[e], t.scale);
-    }
-    if (tail0 + tid < len) stats_add(a, hist, lim, x[tail0 + tid], t.scale);
-  }
+  auto add = [&](int, float x) { stats_add(a, hist, lim, x, t.scale); };
+  if (t.bf16) visit_row<256>((const bf16_t*)t.x + c.start, len, tid, add);
+  else visit_row<256>((const float*)t.x + c.start, len, tid, add);
 
   // fixed-order tree over the 256 per-thread partials
   rs[tid] = a.sum; rq[tid] = a.sumsq; rmn[tid] = a.mn; rmx[tid] = a.mx; rz[tid] = a.zeros; rnf[tid] = a.nonfinite;
@@ -222,7 +192,7 @@ static const double* stats_host_limits() {
 using namespace dtm;
 
 DTM_API int dtm_stats_tensor_bytes() { return (int)sizeof(StatsTensor); }
-DTM_API int dtm_stats_chunk_bytes() { return (int)sizeof(StatsChunk); }
+DTM_API int dtm_stats_chunk_bytes() { return (int)sizeof(ChunkRow); }
 DTM_API int dtm_stats_partial_bytes() { return (int)sizeof(StatsPartial); }
 DTM_API int dtm_stats_result_bytes() { return (int)sizeof(StatsResult); }
 DTM_API int dtm_stats_chunk_size() { return STATS_CHUNK; }
@@ -264,7 +234,7 @@ DTM_API int dtm_tensor_stats(const void* tens, const void* chunks, int nchunks, 
   if (hipStreamWaitEvent(st, uploaded, 0) != hipSuccess) return -2;
   if (hipMemsetAsync(bins, 0, sizeof(unsigned) * (size_t)STATS_BUCKETS * ntens, st) != hipSuccess) return -2;
   hipLaunchKernelGGL(tensor_stats_kernel, dim3(nchunks), dim3(256), 0, st, (const StatsTensor*)tens,
-                     (const StatsChunk*)chunks, d_limits, (unsigned*)bins, (StatsPartial*)partials);
+                     (const ChunkRow*)chunks, d_limits, (unsigned*)bins, (StatsPartial*)partials);
   hipLaunchKernelGGL(tensor_stats_finalize_kernel, dim3(ntens), dim3(256), 0, st, (const StatsTensor*)tens,
                      (const StatsPartial*)partials, (StatsResult*)results);
   return (int)hipGetLastError();

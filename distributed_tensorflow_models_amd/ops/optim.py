@@ -46,6 +46,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._tables import chunk_rows, to_device_bytes
 
 # kernel update rule per kind (LARS is the momentum rule with a per-tensor rate factor; Adam and LAMB have entry
 # points of their own)
@@ -145,7 +146,6 @@ class FusedOptimizer:
         assert tb == 64 and cb == 16, (tb, cb)
         dev = self.params[0].device
         tens = np.zeros((len(self.params), 8), dtype=np.uint64)
-        chunks = []
         self._keep = []
         for i, p in enumerate(self.params):
             st = self.state[p]
@@ -159,8 +159,6 @@ class FusedOptimizer:
             tens[i, :6] = ptrs
             tens[i, 6] = p.numel()
             tens[i, 7] = np.array([st["wd"], st["lr_mult"]], dtype=np.float32).view(np.uint64)[0]
-            for s in range(0, p.numel(), chunk):
-                chunks.append((i, 0, s))
         # EMA-only rows (grad pointer 0): the kernel just moves the shadow towards the buffer
         base = len(self.params)
         if self.ema_buffers:
@@ -170,31 +168,22 @@ class FusedOptimizer:
             tens[base + j, 0] = b.data_ptr()
             tens[base + j, 5] = self.buffer_ema[id(b)].data_ptr()
             tens[base + j, 6] = b.numel()
-            for s in range(0, b.numel(), chunk):
-                chunks.append((base + j, 0, s))
-        ct = np.zeros((len(chunks), 2), dtype=np.int64)
-        for j, (i, _, s) in enumerate(chunks):
-            ct[j, 0] = i  # int t, int pad packed little-endian into first 8 bytes
-            ct[j, 1] = s
-        self._tens_dev = torch.from_numpy(tens.view(np.uint8).reshape(-1).copy()).to(dev)
-        self._chunks_dev = torch.from_numpy(ct.view(np.uint8).reshape(-1).copy()).to(dev)
-        self._nchunks = len(chunks)
+        ct, chunk0, nchunks = chunk_rows([t.numel() for t in self.params + self.ema_buffers], chunk)
+        self._tens_dev = to_device_bytes(tens, dev)
+        self._chunks_dev = to_device_bytes(ct, dev)
+        self._nchunks = len(ct)
         if self.normed:
             # the norm pass: a side table beside the 64-byte tensor rows (first chunk row, row count, LARS flag),
             # its scratch (one fp64 record per chunk row) and its outputs - all allocated here, none in launch()
             ntens = tens.shape[0]
             assert L.dtm_opt_norm_meta_bytes() == 16
             meta = np.zeros((ntens, 4), dtype=np.int32)
-            for j, (i, _, _s) in enumerate(chunks):
-                if meta[i, 1] == 0:
-                    meta[i, 0] = j
-                assert meta[i, 0] + meta[i, 1] == j, "chunk rows of a tensor must be contiguous"
-                meta[i, 1] += 1
+            meta[:, 0], meta[:, 1] = chunk0, nchunks
             for i, p in enumerate(self.params):
                 meta[i, 2] = int(self.state[p]["adapt"])
             self._ntens = ntens
-            self._meta_dev = torch.from_numpy(meta.view(np.uint8).reshape(-1).copy()).to(dev)
-            self._norm_scratch = torch.zeros(int(L.dtm_opt_norm_scratch_bytes(len(chunks), ntens)) // 8,
+            self._meta_dev = to_device_bytes(meta, dev)
+            self._norm_scratch = torch.zeros(int(L.dtm_opt_norm_scratch_bytes(len(ct), ntens)) // 8,
                                              dtype=torch.float64, device=dev)
             self._norms = torch.zeros((ntens, 3), dtype=torch.float32, device=dev)
             self._lr_scale = torch.ones(ntens, dtype=torch.float32, device=dev)

@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._tables import chunk_rows, to_device_bytes
 
 EPS = 1e-12
 
@@ -108,22 +109,14 @@ class SamPerturber:
         assert L.dtm_sam_tensor_bytes() == 40 and L.dtm_sam_chunk_bytes() == 16 and L.dtm_sam_meta_bytes() == 8
         rows = [r for r in self.rows if r[0].numel() > 0]
         tens = np.zeros((len(rows), 5), dtype=np.uint64)
-        meta = np.zeros((len(rows), 2), dtype=np.int32)
-        chunks = []
         for i, (p, g, backup, pcopy) in enumerate(rows):
             tens[i] = [p.data_ptr(), g.data_ptr() if g is not None else 0, backup.data_ptr(),
                        pcopy.data_ptr() if pcopy is not None else 0, p.numel()]
-            meta[i, 0] = len(chunks)
-            for s in range(0, p.numel(), chunk):
-                chunks.append((i, s))
-            meta[i, 1] = len(chunks) - meta[i, 0]
-        ct = np.zeros((len(chunks), 2), dtype=np.int64)
-        for j, (i, s) in enumerate(chunks):
-            ct[j, 0] = i  # int t, int pad packed little-endian into the first 8 bytes
-            ct[j, 1] = s
-        as_dev = lambda a: torch.from_numpy(a.view(np.uint8).reshape(-1).copy()).to(dev)  # noqa: E731
-        self._tens_dev, self._chunks_dev, self._meta_dev = as_dev(tens), as_dev(ct), as_dev(meta)
-        self._nchunks, self._ntens = len(chunks), len(rows)
+        ct, chunk0, nchunks = chunk_rows([r[0].numel() for r in rows], chunk)
+        meta = np.stack([chunk0, nchunks], axis=1).astype(np.int32)
+        self._tens_dev, self._chunks_dev = to_device_bytes(tens, dev), to_device_bytes(ct, dev)
+        self._meta_dev = to_device_bytes(meta, dev)
+        self._nchunks, self._ntens = len(ct), len(rows)
         self._scratch = torch.zeros(max(1, int(L.dtm_sam_scratch_bytes(self._nchunks, self._ntens)) // 8),
                                     dtype=torch.float64, device=dev)
         self._dev = dev

@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._tables import chunk_rows, to_device_bytes
 
 NUM_BUCKETS = 1551
 _limits = None
@@ -100,20 +101,14 @@ class TensorStats:
         T = len(self.tensors)
         tens = np.zeros(T, dtype=np.dtype([("x", "<u8"), ("n", "<u8"), ("scale", "<f4"), ("bf16", "<i4"),
                                            ("chunk0", "<u4"), ("nchunks", "<u4")]))
-        chunks = []
+        ct, chunk0, nchunks = chunk_rows([t.numel() for t in self.tensors], chunk)
         for i, t in enumerate(self.tensors):
-            n = t.numel()
             assert t.data_ptr() % t.element_size() == 0
-            starts = range(0, n, chunk)
-            tens[i] = (t.data_ptr(), n, self.scales[i], int(t.dtype == torch.bfloat16), len(chunks), len(starts))
-            chunks.extend((i, s) for s in starts)
-        ct = np.zeros(len(chunks), dtype=np.dtype([("t", "<i4"), ("pad", "<i4"), ("start", "<i8")]))
-        ct["t"] = [c[0] for c in chunks]
-        ct["start"] = [c[1] for c in chunks]
+            tens[i] = (t.data_ptr(), t.numel(), self.scales[i], int(t.dtype == torch.bfloat16), chunk0[i], nchunks[i])
         dev = self.device
-        self._tens_dev = torch.from_numpy(tens.view(np.uint8).copy()).to(dev)
-        self._chunks_dev = torch.from_numpy(ct.view(np.uint8).copy()).to(dev)
-        self._nchunks = len(chunks)
+        self._tens_dev = to_device_bytes(tens, dev)
+        self._chunks_dev = to_device_bytes(ct, dev)
+        self._nchunks = len(ct)
         self._bins = torch.empty((T, NUM_BUCKETS), dtype=torch.int32, device=dev)  # zeroed by every launch
         self._partials = torch.empty(self._nchunks * L.dtm_stats_partial_bytes(), dtype=torch.uint8, device=dev)
         self._results = torch.empty(T * _RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)

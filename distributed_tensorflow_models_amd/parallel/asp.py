@@ -253,11 +253,11 @@ class ParamStore:
         import numpy as np
 
         from ..ops import _lib
+        from ..ops._tables import chunk_rows, to_device_bytes
         L = _lib.lib()
         tb, chunk = L.dtm_opt_tensor_bytes(), L.dtm_opt_chunk_size()
         assert tb == 64, tb
         tens = np.zeros((len(self.params), 8), dtype=np.uint64)
-        chunks = []
         for i, p in enumerate(self.params):
             sh = self.shards[i]
             tens[i, 0] = sh["param"].data_ptr()
@@ -265,15 +265,11 @@ class ParamStore:
             tens[i, 3] = sh["s2"].data_ptr() if "s2" in sh else 0
             tens[i, 6] = p.numel()
             tens[i, 7] = np.array([self.wd[i], 1.0], dtype=np.float32).view(np.uint64)[0]
-            for st in range(0, p.numel(), chunk):
-                chunks.append((i, st))
-        ct = np.zeros((len(chunks), 2), dtype=np.int64)
-        for j, (i, st) in enumerate(chunks):
-            ct[j, 0], ct[j, 1] = i, st
+        ct, _, _ = chunk_rows([p.numel() for p in self.params], chunk)
         dev = self.params[0].device
         self._ftens = tens
-        self._fchunks = torch.from_numpy(ct.view(np.uint8).reshape(-1).copy()).to(dev)
-        self._fnchunks = len(chunks)
+        self._fchunks = to_device_bytes(ct, dev)
+        self._fnchunks = len(ct)
         self._fring = [(torch.empty(tens.nbytes, dtype=torch.uint8).pin_memory(),
                         torch.zeros(3, dtype=torch.float32).pin_memory(), None) for _ in range(4)]
         self._fi = 0

@@ -1392,18 +1392,34 @@ __device__ __forceinline__ void glds16(const void* gptr, const void* lds) {
 // (A form with the block-output dgrads' side inputs - add_src, x_raw, ReLU mask bytes, act_r - LDS-DMA'd one tile
 // ahead was faster per kernel on the 28x28 stage but slower at step level: its 1-block/CU LDS footprint locks the
 // side-stream weight gradients out of the CUs it holds; profiles/ab/r4_ab_sside_alds.log.  Removed.)
-template <int PT, int CT, int NKT, bool PRO, bool STEM = false, int NBUF = 2, bool SIDE = true>
-__global__ __launch_bounds__(256) void conv1x1_stream_kernel(ConvNTArgs a, int ntiles) {
-  constexpr int WP = PT / 2, WC = CT / 2;
+//
+// NT = 512 (tile ids 34 / 35): the 8-wave form for the 128- / 256-deep expansion convs.  Their resident weight tile
+// (64 KiB) allows one block per CU, and one wave per SIMD cannot hide the DMA, LDS and store latencies; eight waves
+// (2 pixel halves x 4 channel quarters) put two on every SIMD over ONE weight tile and ONE pixel ring.  Forward
+// forms only (SIDE = false).  They replace the 8-wave 256x256 tile and keep ITS statistics rows, bit for bit: a worker
+// walks whole 256-pixel groups (four consecutive 64-pixel tiles), every chunk column is summed by 16 threads over the
+// rows g, g + 16, ... of the group in that tile's order, and one partial row per group is reduced over the 16 threads
+// in order (the staged tail of conv_nt_epi_tail<256, 256, ..., 512>) - so the BatchNorm statistics, and with them the
+// training step, compute what they computed on that tile.
+template <int PT, int CT, int NKT, bool PRO, bool STEM = false, int NBUF = 2, bool SIDE = true, int NT = 256>
+__global__ __launch_bounds__(NT) void conv1x1_stream_kernel(ConvNTArgs a, int ntiles) {
+  constexpr int NW = NT / 64;                    // waves: 2 pixel halves x NW / 2 channel slices
+  static_assert(NT == 256 || (NT == 512 && !SIDE && !STEM), "4 waves, or the 8-wave forward form");
+  constexpr int WP = PT / 2, WC = CT / (NW / 2);
   constexpr int TP = WP / 16, TC = WC / 16;
-  constexpr int AI = PT / 32, WI = CT / 32;      // 1-KiB DMA pieces per wave per 64-k sub-tile
+  constexpr int AI = PT / (8 * NW), WI = CT / (8 * NW);  // 1-KiB DMA pieces per wave per 64-k sub-tile
+  static_assert(AI >= 1 && WI >= 1 && PT % (8 * NW) == 0 && CT % (8 * NW) == 0, "whole DMA pieces per wave");
   constexpr int ABUF = NKT * PT * 128;           // one pixel tile, all k
   constexpr int WBUF = NKT * CT * 128;
   constexpr int OROW = CT * 2 + 16;
   constexpr int STG = PT * OROW > 16384 ? PT * OROW : 16384;
-  constexpr int NIT = PT * (CT / 8) / 256;      // exact staged stores per thread per tile
+  constexpr int NIT = PT * (CT / 8) / NT;       // exact staged stores per thread per tile
   constexpr int MAXC = 512;
   constexpr int OFF_A = WBUF, OFF_S = WBUF + NBUF * ABUF, OFF_P = OFF_S + STG;
+  constexpr bool TR = NT == 512;                 // statistics rows per 256-pixel group (see above)
+  constexpr int NSTAT = (CT / 8) * 16;           // TR: threads that hold statistics sums (chunk column x 16 row classes)
+  static_assert(!TR || (NBUF == 2 && PT == 64 && NSTAT <= NT && STG >= NSTAT * 64), "group rows: table in the staging area");
+  static_assert(OFF_P + (PRO ? MAXC * 8 : 0) <= 160 * 1024, "LDS budget");
   constexpr int NDMA = NKT * AI;                // DMA instructions per thread per tile
   static_assert(NBUF == 2 || NBUF == 3, "ring depth");
   static_assert(2 * NIT + NDMA <= 63, "vmcnt range");
@@ -1425,18 +1441,18 @@ __global__ __launch_bounds__(256) void conv1x1_stream_kernel(ConvNTArgs a, int n
   float* s_scale = (float*)(smem + OFF_P);
   float* s_shift = s_scale + MAXC;
   if constexpr (PRO) {
-    for (int c = tid; c < a.C; c += 256) { s_scale[c] = a.in_scale[c]; s_shift[c] = a.in_shift[c]; }
+    for (int c = tid; c < a.C; c += NT) { s_scale[c] = a.in_scale[c]; s_shift[c] = a.in_shift[c]; }
   }
   // resident weight tile: NKT sub-tiles [CT][64] (128-B rows, chunk ^= row & 7)
 #pragma unroll
   for (int kt = 0; kt < NKT; ++kt) {
 #pragma unroll
     for (int j = 0; j < WI; ++j) {
-      const int row = c0 + 8 * (wave + 4 * j) + lr;
+      const int row = c0 + 8 * (wave + NW * j) + lr;
       const int k = kt * 64 + ch * 8;
       const bool v = (row < a.K) & (k < a.Kg);
       const char* src = wg + (size_t)(uint32_t)((row * a.Kg + k) * 2);
-      __builtin_amdgcn_global_load_lds((gvoid*)(v ? src : zg), (lvoid*)(smem + kt * CT * 128 + (wave + 4 * j) * 1024),
+      __builtin_amdgcn_global_load_lds((gvoid*)(v ? src : zg), (lvoid*)(smem + kt * CT * 128 + (wave + NW * j) * 1024),
                                        16, 0, 0);
     }
   }
@@ -1450,7 +1466,7 @@ __global__ __launch_bounds__(256) void conv1x1_stream_kernel(ConvNTArgs a, int n
     if constexpr (STEM) {
 #pragma unroll
       for (int j = 0; j < AI; ++j) {
-        const int m = t * PT + 8 * (wave + 4 * j) + lr;
+        const int m = t * PT + 8 * (wave + NW * j) + lr;
         const uint32_t mm = m < a.M ? (uint32_t)m : 0u;
         const uint32_t n = fdiv(mm, a.fd_PQ), rem = mm - n * (a.P * a.Q);
         const uint32_t p = fdiv(rem, a.fd_Q), q = rem - p * a.Q;
@@ -1462,12 +1478,12 @@ __global__ __launch_bounds__(256) void conv1x1_stream_kernel(ConvNTArgs a, int n
       const int k = kt * 64 + ch * 8;
 #pragma unroll
       for (int j = 0; j < AI; ++j) {
-        const int m = t * PT + 8 * (wave + 4 * j) + lr;
+        const int m = t * PT + 8 * (wave + NW * j) + lr;
         const bool v = (m < a.M) & (k < a.Kg);
         const char* src = STEM ? xg + (size_t)(pix[j] + (uint32_t)((k >> 5) * a.Win * 8 + (k & 31) * 2))
                                : xg + (size_t)(uint32_t)(m * a.pix_bytes + k * 2);
         srcs[kt * AI + j] = v ? src : zg;
-        glds16(srcs[kt * AI + j], base + kt * PT * 128 + (wave + 4 * j) * 1024);
+        glds16(srcs[kt * AI + j], base + kt * PT * 128 + (wave + NW * j) * 1024);
       }
     }
   };
@@ -1483,9 +1499,9 @@ __global__ __launch_bounds__(256) void conv1x1_stream_kernel(ConvNTArgs a, int n
         const float sh[8] = {h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
 #pragma unroll
         for (int j = 0; j < AI; ++j) {
-          const int m = t * PT + 8 * (wave + 4 * j) + lr;
+          const int m = t * PT + 8 * (wave + NW * j) + lr;
           if (m < a.M) {
-            uint4* pp = (uint4*)(base + kt * PT * 128 + (wave + 4 * j) * 1024 + lane * 16);
+            uint4* pp = (uint4*)(base + kt * PT * 128 + (wave + NW * j) * 1024 + lane * 16);
             const uint4 q = *pp;
             uint32_t u[4] = {q.x, q.y, q.z, q.w};
 #pragma unroll
@@ -1508,16 +1524,19 @@ __global__ __launch_bounds__(256) void conv1x1_stream_kernel(ConvNTArgs a, int n
   for (int e = 0; e < 8; ++e) { ssum[e] = 0.f; ssq[e] = 0.f; }
 #pragma unroll
   for (int e = 0; e < 24; ++e) aacc[e] = 0.f;
-  int t = by0;
   const int gy = gridDim.y;
+  // TR: ntiles = 4 x the 256-pixel groups; worker y walks groups y, y + gy, ... tile by tile (tiles past M are empty)
+  int t = TR ? 4 * by0 : by0;
+  auto nxt = [&](int u) { return TR ? ((u & 3) == 3 ? u + 4 * gy - 3 : u + 1) : u + gy; };
   if (t < ntiles) issue(t, 0);
   if (NBUF == 3 && t + gy < ntiles) issue(t + gy, 1);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();  // weights (+ prologue affine) resident, tile 0 (and 1) landed
   int buf = 0;
-  for (int it = 0; t < ntiles; ++it, t += gy) {
+  for (int it = 0; t < ntiles; ++it, t = nxt(t)) {
     if constexpr (NBUF == 2) {
       // this wave's DMA of tile t has landed once at most the previous epilogue's NIT stores are pending
+      // (TR: a group row's stores may follow them - the wait is then only stricter)
       if (it > 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NIT) : "memory");
     } else if (it >= 2) {
       // issued after this wave's DMA of tile t: stores(it-2), the DMA of tile t+gy (if any), stores(it-1)
@@ -1528,7 +1547,7 @@ __global__ __launch_bounds__(256) void conv1x1_stream_kernel(ConvNTArgs a, int n
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();  // tile t visible; the slot read last iteration and the stage area are free
     if constexpr (NBUF == 2) {
-      if (t + gy < ntiles) issue(t + gy, buf ^ 1);
+      if (nxt(t) < ntiles) issue(nxt(t), buf ^ 1);
     } else {
       if (t + 2 * gy < ntiles) issue(t + 2 * gy, buf == 0 ? 2 : buf - 1);
     }
@@ -1561,8 +1580,57 @@ __global__ __launch_bounds__(256) void conv1x1_stream_kernel(ConvNTArgs a, int n
             acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bf[j], acc[i][j], 0, 0, 0);
       }
     }
-    conv_nt_epilogue<PT, CT, WP, WC, 1, true, true, true, true, 256, SIDE>(a, acc, smem + OFF_S, t * PT, c0, t, ssum,
-                                                                           ssq, nullptr, nullptr, aacc);
+    float dsum[8], dsq[8];  // (TR, CT < 256: the tail's own column sums are not the 256x256 tile's - unused)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { dsum[e] = 0.f; dsq[e] = 0.f; }
+    constexpr bool OWN = TR && CT != 256;
+    conv_nt_epilogue<PT, CT, WP, WC, 1, true, true, true, true, NT, SIDE>(a, acc, smem + OFF_S, t * PT, c0, t,
+                                                                          OWN ? dsum : ssum, OWN ? dsq : ssq, nullptr,
+                                                                          nullptr, aacc);
+    if constexpr (TR) {
+      if (a.stats) {
+        constexpr int CPR = CT / 8;
+        if constexpr (OWN) {
+          // the staged tile once more: thread (column c, class g) adds rows g, g + 16, g + 32, g + 48 - with CT = 256
+          // that is the tail's own mapping (SACC) and this pass is not needed
+          if (tid < NSTAT) {
+            const int c = tid % CPR, g = tid / CPR;
+            const int kc = c0 + c * 8;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              const int row = g + 16 * j;
+              if (t * PT + row < a.M && kc < a.K) {
+                const uint4 v = *(const uint4*)(smem + OFF_S + row * OROW + c * 16);
+                const float q[8] = {lo_bf(v.x), hi_bf(v.x), lo_bf(v.y), hi_bf(v.y),
+                                    lo_bf(v.z), hi_bf(v.z), lo_bf(v.w), hi_bf(v.w)};
+#pragma unroll
+                for (int e = 0; e < 8; ++e) { ssum[e] += q[e]; ssq[e] = fmaf(q[e], q[e], ssq[e]); }
+              }
+            }
+          }
+        }
+        if ((t & 3) == 3) {  // the group is complete: its partial row, the 16 classes summed in order
+          epi_barrier<true>();
+          float* red = (float*)(smem + OFF_S);  // [NSTAT][16]
+          if (tid < NSTAT) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) { red[tid * 16 + e] = ssum[e]; red[tid * 16 + 8 + e] = ssq[e]; }
+          }
+          epi_barrier<true>();
+          float* prow = a.stats + (size_t)(t >> 2) * (2 * a.K);
+          for (int o = tid; o < CPR * 16; o += NT) {
+            const int c = o >> 4, e = o & 15;
+            float r = 0.f;
+#pragma unroll 4
+            for (int k = 0; k < 16; ++k) r += red[((c + k * CPR) << 4) + e];
+            const int kk = c0 + c * 8 + (e & 7);
+            if (kk < a.K) prow[(e < 8 ? 0 : a.K) + kk] = r;
+          }
+#pragma unroll
+          for (int e = 0; e < 8; ++e) { ssum[e] = 0.f; ssq[e] = 0.f; }
+        }
+      }
+    }
 #pragma unroll
     for (int i = 0; i < NKT * AI; ++i) asm volatile("" ::"v"(srcs[i]));
     buf = buf + 1 == NBUF ? 0 : buf + 1;
@@ -1570,12 +1638,14 @@ __global__ __launch_bounds__(256) void conv1x1_stream_kernel(ConvNTArgs a, int n
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   // one partial row per worker (pixel-tile walker): [sum(K) | sumsq(K)] statistics, or the dgrad's
   // activation-backward sums [sum g*x | sum g (| sum g*r | sum g)] (SIDE)
-  if (a.stats) worker_row<CT>((float*)(smem + OFF_S), ssum, ssq, a.stats + (size_t)by0 * (2 * a.K), c0, a.K);
-  if (SIDE && a.act_x && a.act_sums) {
-    const int rw = a.act_r ? 4 : 2;
-    float* row = a.act_sums + (size_t)by0 * (rw * a.K);
-    worker_row<CT>((float*)(smem + OFF_S), aacc, aacc + 8, row, c0, a.K);
-    if (a.act_r) worker_row<CT>((float*)(smem + OFF_S), aacc + 16, aacc + 8, row + 2 * a.K, c0, a.K);
+  if constexpr (!TR) {
+    if (a.stats) worker_row<CT>((float*)(smem + OFF_S), ssum, ssq, a.stats + (size_t)by0 * (2 * a.K), c0, a.K);
+    if (SIDE && a.act_x && a.act_sums) {
+      const int rw = a.act_r ? 4 : 2;
+      float* row = a.act_sums + (size_t)by0 * (rw * a.K);
+      worker_row<CT>((float*)(smem + OFF_S), aacc, aacc + 8, row, c0, a.K);
+      if (a.act_r) worker_row<CT>((float*)(smem + OFF_S), aacc + 16, aacc + 8, row + 2 * a.K, c0, a.K);
+    }
   }
 }
 
@@ -2747,29 +2817,33 @@ static bf16_t* dump_chunk() {
 
 // persistent streaming 1x1 kernel: blocks = resident capacity (occupancy x CUs), channel tiles x
 // pixel-tile workers
-template <int PT, int CT, int NKT, bool PRO, bool STEM = false, int NBUF = 2, bool SIDE = true>
+// (test-only cap on the worker count, 0 = off: each worker then walks several pixel tiles of a tiny input)
+static int g_stream_workers_cap = 0;
+DTM_API void dtm_conv_set_stream_workers_cap(int n) { g_stream_workers_cap = n; }
+template <int PT, int CT, int NKT, bool PRO, bool STEM = false, int NBUF = 2, bool SIDE = true, int NT = 256>
 static int stream_workers_k(const ConvNTArgs& a) {
   static int occ = 0;
   if (!occ) {
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, conv1x1_stream_kernel<PT, CT, NKT, PRO, STEM, NBUF, SIDE>,
-                                                     256, 0) !=
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, conv1x1_stream_kernel<PT, CT, NKT, PRO, STEM, NBUF, SIDE, NT>,
+                                                     NT, 0) !=
             hipSuccess || occ <= 0)
       occ = 1;
   }
   const int ctiles = (a.K + CT - 1) / CT;
-  const int ntiles = (a.M + PT - 1) / PT;
+  const int ntiles = NT == 512 ? (a.M + 255) / 256 : (a.M + PT - 1) / PT;  // (8-wave forms: 256-pixel groups)
   int workers = (occ * device_cus() + ctiles - 1) / ctiles;
+  if (g_stream_workers_cap > 0 && workers > g_stream_workers_cap) workers = g_stream_workers_cap;
   if (workers > ntiles) workers = ntiles;
   if (workers < 1) workers = 1;
   return workers;
 }
 
-template <int PT, int CT, int NKT, bool PRO, bool STEM = false, int NBUF = 2, bool SIDE = true>
+template <int PT, int CT, int NKT, bool PRO, bool STEM = false, int NBUF = 2, bool SIDE = true, int NT = 256>
 static void launch_stream_k(const ConvNTArgs& a, hipStream_t st) {
   const int ctiles = (a.K + CT - 1) / CT;
-  const int ntiles = (a.M + PT - 1) / PT;
-  hipLaunchKernelGGL((conv1x1_stream_kernel<PT, CT, NKT, PRO, STEM, NBUF, SIDE>),
-                     dim3(ctiles, stream_workers_k<PT, CT, NKT, PRO, STEM, NBUF, SIDE>(a)), dim3(256), 0, st, a, ntiles);
+  const int ntiles = NT == 512 ? 4 * ((a.M + 255) / 256) : (a.M + PT - 1) / PT;
+  hipLaunchKernelGGL((conv1x1_stream_kernel<PT, CT, NKT, PRO, STEM, NBUF, SIDE, NT>),
+                     dim3(ctiles, stream_workers_k<PT, CT, NKT, PRO, STEM, NBUF, SIDE, NT>(a)), dim3(NT), 0, st, a, ntiles);
 }
 
 static bool stem_stream_ok(const ConvNTArgs& a) {
@@ -2796,12 +2870,21 @@ static int stream_workers(const ConvNTArgs& a) {
   return stream_workers_k<64, CT, NKT, false, false, 2, false>(a);
 }
 
+// the 8-wave forms (tile ids 34 / 35; forward only, with or without the BN-apply prologue)
+template <int CT, int NKT>
+static void launch_stream8(const ConvNTArgs& a, hipStream_t st) {
+  if (a.in_scale) launch_stream_k<64, CT, NKT, true, false, 2, false, 512>(a, st);
+  else launch_stream_k<64, CT, NKT, false, false, 2, false, 512>(a, st);
+}
+
 // the stem forward as a persistent stream: -1: DTM_STEM_STREAM env (default 1), 0 off, 1 on (3-slot ring),
 // 2 on with the 2-slot ring (A/B knob)
 static int g_stem_stream = 1;  // A/B API dtm_conv_set_stem_stream (2 = the 2-slot ring)
 DTM_API void dtm_conv_set_stem_stream(int on) { g_stem_stream = on; }
-// statistics partial rows of the streaming kernel (tile id 30 / 31 / 33): one per worker
+// statistics partial rows of the streaming kernel: one per worker (tile id 30 / 31 / 33); the 8-wave forms (34 / 35)
+// write the 256x256 tile's rows, one per 256-pixel group
 static int stream_rows(const ConvNTArgs& a, int id) {
+  if (id == 34 || id == 35) return (a.M + 255) / 256;
   if (id == 33) return g_stem_stream == 2 ? stream_workers_k<64, 64, 4, false, true, 2, false>(a)
                                           : stream_workers_k<64, 64, 4, false, true, 3, false>(a);
   const bool k1 = a.Kg <= 64;
@@ -2811,9 +2894,12 @@ static int stream_rows(const ConvNTArgs& a, int id) {
   return k1 ? stream_workers<64, 1>(a) : stream_workers<64, 2>(a);
 }
 
-static bool stream_ok(const ConvNTArgs& a) {
+// id: 30 / 31 (the 4-wave forms, reductions up to 128), 34 / 35 (the 8-wave forms: up to 128 / 256, no dgrad post-ops)
+static bool stream_ok(const ConvNTArgs& a, int id = 30) {
+  const int kmax = id == 35 ? 256 : 128;
+  if ((id == 34 || id == 35) && (a.add_src || a.act_x)) return false;
   return !a.bias && !a.relu && a.R == 1 && a.S == 1 && a.stride == 1 && a.pad_h == 0 && a.pad_w == 0 && a.Hv == a.Hin && a.Wv == a.Win &&
-         a.P == a.Hin && a.Q == a.Win && a.Kg % 64 == 0 && a.Kg <= 128 && a.K % 8 == 0 &&
+         a.P == a.Hin && a.Q == a.Win && a.Kg % 64 == 0 && a.Kg <= kmax && a.K % 8 == 0 &&
          (!a.in_scale || a.C <= 512) && a.dump != nullptr && a.ostr == 1;
 }
 
@@ -2847,7 +2933,8 @@ static void launch_nt_act(const ConvNTArgs& a, hipStream_t st) {
 // profiles/ab/README.md): 0 = 128 pix x 128 ch register-staged (4 waves 2x2 of 64x64), 3 / 4 = 128 x 64 /
 // 64 x 128 register-staged with a single LDS buffer (more resident blocks), 21 / 24 / 26 / 32 = LDS-DMA
 // pipelined 128x128 / 256x64 / 128x64 / 256x32, 30 / 31 = the persistent streaming 1x1 kernel (128 / 64
-// channels), 40 = the 8-wave 256x256 tile.  DTM_CONV_TILE forces one (sweeps: tools/conv_tile_sweep.py).
+// channels), 34 / 35 = its 8-wave forms for the 128- / 256-deep reductions (64 pix x 256 / 128 channels, forward
+// only), 40 = the 8-wave 256x256 tile.  DTM_CONV_TILE forces one (sweeps: tools/conv_tile_sweep.py).
 // the direct 3x3 kernel (tile id 60): -1: DTM_DIRECT3X3 env (default 1), 0 / 1: A/B knob
 static int g_direct3 = 1;  // A/B API dtm_conv_set_direct3
 DTM_API void dtm_conv_set_direct3(int on) { g_direct3 = on; }
@@ -2920,6 +3007,10 @@ static int g_tile_w8 = 1;  // A/B knob: the 8-wave tile in the shape policy (dtm
 // the act sums accumulate per worker, profiles/ab/r3_ab_stream_act.log)
 static int g_stream_act = 0;
 DTM_API void dtm_conv_set_stream_act(int on) { g_stream_act = on; }
+// A/B knob (dtm_conv_set_stream8): the 8-wave streaming forms in the shape policy, one bit per shape class -
+// 1: the 128-deep expansion convs (tile 34), 2: the 256-deep ones (tile 35)
+static int g_stream8 = 3;
+DTM_API void dtm_conv_set_stream8(int classes) { g_stream8 = classes; }
 static int g_kwide = 1;    // A/B knob: 64-channel tiles for K % 128 in (0, 64] (dtm_conv_set_kwide)
 DTM_API void dtm_conv_set_kwide(int on) { g_kwide = on; }
 DTM_API void dtm_conv_set_w8(int on) { g_tile_w8 = on; }
@@ -2973,9 +3064,18 @@ static TileCfg pick_tile_impl(const ConvNTArgs& a, bool stats) {
   else if (id == -1 && a.Kg == 64 && stream_ok(a) && (g_stream_act || !a.act_x) &&
            (!g_policy2 || a.K % 128 == 0 || a.K <= 64))  // (v2: no partial channel tiles: 35x35 ->288 -33 %)
     id = a.K >= 128 ? 30 : 31;
+  // the 8-wave streaming forms: the 1x1 stride-1 expansion forwards with BN statistics whose reduction is 128 / 256
+  // deep (ResNet-50 conv3 of stages 2 / 3 and the stride-1 stage-2 shortcut), where the 256x256 tile ran so far (its
+  // rule below: whole 256-channel tiles, >= 150 of them) - the only sizes they were measured at
+  else if (id == -1 && stats && !a.in_scale && g_tile_w8 && a.K % 256 == 0 &&
+           (long)((a.M + 255) / 256) * (a.K / 256) >= 150 &&
+           (((g_stream8 & 1) && a.Kg == 128 && stream_ok(a, 34)) || ((g_stream8 & 2) && a.Kg == 256 && stream_ok(a, 35))))
+    id = a.Kg == 128 ? 34 : 35;
   if (id == -1 && a.act_x && g_act_tile >= 0) id = g_act_tile;  // (A/B: the non-streaming act dgrads)
   // (the persistent streaming 1x1 kernel: the 64-deep 56x56 expand / reduce layers and their dgrads are
-  // HBM streams: -20..-33 % (tools/conv_tile_sweep.py); at Kg 128 its 1 block/CU loses)
+  // HBM streams: -20..-33 % (tools/conv_tile_sweep.py); at Kg 128 its 4-wave form, 1 block/CU, loses - the 8-wave
+  // forms 34 / 35 above take the 128- / 256-deep expansion forwards with statistics: 28x28 128 -> 512 93.5 -> 64.0 us,
+  // 14x14 256 -> 1024 69.3 -> 57.5 us, ResNet-50 step -1.35 %: profiles/ab/stream8_sweep.txt, ab_stream8.log)
   // the 8-wave 256x256 tile (id 40) where it fills the chip: >= ~150 tiles (one round, 58-100 % of the
   // CUs), and not on the many-tile short-reduction layers without statistics (their 4-wave tiles stream
   // better).  Measured per ResNet-50 layer (tools/conv_tile_sweep.py STATS=1, profiles/r2_conv_tiles_w8.txt):
@@ -3026,8 +3126,8 @@ static TileCfg pick_tile_impl(const ConvNTArgs& a, bool stats) {
   if (id == 40 && g_tile_pp && g_tile_env != 40) id = 41;
   if (id == 41 && a.K % 8) id = 40;  // (the ping-pong tile has only the LDS-staged epilogue)
   if (id == 40 || id == 41) return {id, 256, 2};
-  if (id == 30 || id == 31) {
-    if (stream_ok(a)) return {id, 64, 2};
+  if (id == 30 || id == 31 || id == 34 || id == 35) {
+    if (stream_ok(a, id)) return {id, 64, 2};
     id = a.K <= 64 ? 3 : 4;
   }
   if (id == 3) return {id, 128, 4};
@@ -3058,6 +3158,10 @@ static void dispatch_ud(const ConvNTArgs& a, const TileCfg& t, hipStream_t st) {
   else if (t.id == 30 && UD == 1) {
     if (a.Kg <= 64) launch_stream<128, 1>(a, st);
     else launch_stream<128, 2>(a, st);
+  } else if (t.id == 34 && UD == 1) {
+    launch_stream8<256, 2>(a, st);
+  } else if (t.id == 35 && UD == 1) {
+    launch_stream8<128, 4>(a, st);
   } else if (t.id == 60 && UD == 1) {
     launch_direct(a, st);
   } else if (t.id == 33 && UD == 1) {
@@ -3083,7 +3187,7 @@ DTM_API void dtm_conv_set_tile(int id) { g_tile_env = id; }
 static void dispatch_nt(const ConvNTArgs& a, int ud, const TileCfg& t, hipStream_t st) {
   // (a split launch: dispatch_split records what it runs; the persistent / direct kernels exist for UD = 1 only,
   // dispatch_ud<2> runs tile 0 in their place)
-  g_last_nt_tile = (ud != 1 && (t.id == 30 || t.id == 31 || t.id == 33 || t.id == 60)) ? 0 : t.id;
+  g_last_nt_tile = (ud != 1 && (t.id == 30 || t.id == 31 || t.id == 33 || t.id == 34 || t.id == 35 || t.id == 60)) ? 0 : t.id;
   if (ud == 1) dispatch_ud<1>(a, t, st);
   else dispatch_ud<2>(a, t, st);
 }
@@ -3159,7 +3263,7 @@ static int conv_fwd_impl(const void* x, const void* w, void* y, bool stats, cons
   TileCfg tc = pick_tile(a, stats);
   // (merged-sibling stores happen in the LDS-staged epilogue only: K % 8 == 0 above; the persistent / direct
   // kernels have their own store paths, so a split launch the policy sends there takes the 64x128 tile instead)
-  if (nsplit > 0 && (tc.id == 30 || tc.id == 31 || tc.id == 33 || tc.id == 60)) tc = {4, 64, 2};
+  if (nsplit > 0 && (tc.id == 30 || tc.id == 31 || tc.id == 33 || tc.id == 34 || tc.id == 35 || tc.id == 60)) tc = {4, 64, 2};
   // merged heads: the pipelined 128x128 tile unless the policy took the 8-wave one - measured on every Inception-v3
   // head shape (tools/split_tile_sweep.py, profiles/r4/r4_split_tile_sweep.log): 799 -> ~765 us per step, e.g.
   // 17x17 768 -> 640 85 -> 77 us, 35x35 288 -> 240 84 -> 80 us (the policy's 64x128 / 128x64 picks)
@@ -3182,7 +3286,7 @@ static int conv_fwd_impl(const void* x, const void* w, void* y, bool stats, cons
     // one per streaming / direct worker; one per pixel tile (staged epilogue, K % 8 == 0); else per (pixel
     // tile, pixel wave)
     rows = tc.id == 60 ? direct_workers(a)
-           : (tc.id == 30 || tc.id == 31 || tc.id == 33) ? stream_rows(a, tc.id)
+           : (tc.id == 30 || tc.id == 31 || (tc.id >= 33 && tc.id <= 35)) ? stream_rows(a, tc.id)
                                                           : ((a.M + tc.PT - 1) / tc.PT) * ((a.K & 7) == 0 ? 1 : tc.NWP);
     float* ws = dtm_ws_get_stream((size_t)rows * 2 * d->K, stream);
     if (!ws) return -4;
@@ -3387,7 +3491,7 @@ static int conv_dgrad_impl(const void* dy, const void* wt, void* dx, const ConvD
       if (lt[nl].id == 60) direct_setup(b);
       // act partial rows: one per pixel tile, or one per worker for the persistent kernels
       lrows[nl] = lt[nl].id == 60 ? direct_workers(b)
-                  : (lt[nl].id == 30 || lt[nl].id == 31) ? stream_rows(b, lt[nl].id)
+                  : (lt[nl].id == 30 || lt[nl].id == 31 || lt[nl].id == 34 || lt[nl].id == 35) ? stream_rows(b, lt[nl].id)
                                                          : (b.M + lt[nl].PT - 1) / lt[nl].PT;
       rows += lrows[nl];
       la[nl++] = b;

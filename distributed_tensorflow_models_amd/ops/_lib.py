@@ -173,6 +173,8 @@ _SIGS = {
     "dtm_compute_cus_api": (_I, []),
     "dtm_cu_hog": (_I, [_I, _F, _P]),
     "dtm_conv_set_stream_act": (None, [_I]),
+    "dtm_conv_set_stream8": (None, [_I]),
+    "dtm_conv_set_stream_workers_cap": (None, [_I]),
     "dtm_conv_set_act_tile": (None, [_I]),
     "dtm_stem_pack": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "dtm_dropout": (_I, [_P, _P, _L, _I, _F, ctypes.c_ulonglong, _P, _P]),

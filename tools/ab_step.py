@@ -9,7 +9,7 @@ for K = 64), wdir (0/1: the direct 3x3 weight gradient for 32 input channels), s
 64x256 tile), aocc (0-3: occupancy variants of the register-staged dgrads with post-ops), nocc (the same for
 their launches without side inputs), kwide (0/1: 64-channel
 tiles for K % 128 <= 64), few (0/1: streaming few-row slab reduction), sact (0/1: streaming 1x1 kernel for act
-dgrads), k32 (0/1: 256x32 tile for <=32-channel spatial convs), cpt (16-B chunks per thread of the BN-stream grids),
+dgrads), s8 (bits: the 8-wave streaming 1x1 forms in the policy, 1 = the 128-deep expansion convs, 2 = the 256-deep), k32 (0/1: 256x32 tile for <=32-channel spatial convs), cpt (16-B chunks per thread of the BN-stream grids),
 pol2 (0/1: v2 conv tile-policy rules), sstr (0/1/2: the stem forward as a persistent stream, 3- / 2-slot ring), wgs
 (0/1: conv+BN weight gradients on a side stream), scu (percent of the CUs the side-stream wgrads size their split-K
 grid for), wcu / swc (the same for the main-stream / stem wgrads), dir3 (0/1: direct 3x3 kernel for C in {32, 64}),
@@ -75,6 +75,7 @@ def apply(cfg):
     L.dtm_conv_set_kwide(int(cfg.get("kwide", "1")))
     L.dtm_set_reduce_few(int(cfg.get("few", "1")))
     L.dtm_conv_set_stream_act(int(cfg.get("sact", "0")))
+    L.dtm_conv_set_stream8(int(cfg.get("s8", "3")))
     L.dtm_conv_set_act_tile(int(cfg.get("atile", "-1")))
     L.dtm_conv_set_policy2(int(cfg.get("pol2", "1")))
     L.dtm_set_grid_cpt(int(cfg.get("cpt", "8")))

@@ -17,6 +17,7 @@ from .ops import nn as F
 from .ops import prune as _prune
 from .ops import sam as _sam
 from .ops.optim import FusedOptimizer
+from .ops.compress import GradCompress  # noqa: F401  (TrainStep(grad_compress=GradCompress(...)))
 from .ops.prune import PruneConfig  # noqa: F401  (TrainStep(prune=PruneConfig(...)))
 from .ops.sam import SamConfig  # noqa: F401  (TrainStep(sam=SamConfig(...)))
 from .parallel.bsp import BSPDataParallel, BufferSync
@@ -141,7 +142,7 @@ class TrainStep:
                  grad_comm_dtype=None, ema_buffers=True, bn_sync_every=1, wgrad_stream=None, bsp_check=None,
                  overlap=True, force_comm=False, graph_comm=False, lars_eeta=0.001, lars_epsilon=0.0,
                  clip_global_norm=None, beta1=0.9, beta2=0.999, accum_steps=1, mix=None, rank=None,
-                 distill=None, prune=None, lars_skip=None, sam=None):
+                 distill=None, prune=None, lars_skip=None, sam=None, grad_compress=None):
         # epsilon None: the optimizer's own default (1e-10; Adam 1e-8; LAMB 1e-6); beta1 / beta2: Adam and LAMB
         # lars_skip: predicate on a parameter, True = no trust ratio for it under lars / lamb (default: ndim <= 1)
         # accum_steps N: a call runs N micro-batches, sums their gradients (parallel/bsp.py begin_micro /
@@ -159,6 +160,16 @@ class TrainStep:
         # masks so far applied (so a mask only shrinks), and on every step the masks are applied to the weights,
         # their bf16 copies and EMA shadows, before the dgrad copies are re-derived.  Neither pass looks at the skip
         # flag.  None: nothing is constructed, today's launches and bits.
+        # grad_compress: an ops.compress.GradCompress - top-k sparsification of the gradient exchange with error
+        # feedback (parallel/bsp.py): each plain bucket sends the k largest-magnitude entries of residual + gradient.
+        # The NaN guard, the norm pass, clipping and the optimizer read the decompressed buffer.  Whether a step sends
+        # packets is a host decision (begin_step), so captured steps are refused.  None: nothing is constructed,
+        # today's launches and bits.
+        if grad_compress is not None and not isinstance(grad_compress, GradCompress):
+            raise ValueError("grad_compress must be an ops.compress.GradCompress or None, got %r" % (grad_compress,))
+        if grad_compress is not None and use_graph:
+            raise ValueError("grad_compress is not combined with use_graph: the dense warm-up is a host decision per "
+                             "step")
         if prune is not None and not isinstance(prune, PruneConfig):
             raise ValueError("prune must be an ops.prune.PruneConfig or None, got %r" % (prune,))
         self.prune = prune
@@ -209,7 +220,8 @@ class TrainStep:
         # bsp_check (or DTM_BSP_CHECK=1): assert every gradient write precedes its bucket's all-reduce (debug)
         # force_comm: issue the collectives even with one rank (tests of the RCCL path on a one-GPU box)
         self.dp = BSPDataParallel(params, bucket_mb, process_group, comm_dtype=grad_comm_dtype, overlap=overlap,
-                                  check=bsp_check, names=list(model.named_parameters()), force_comm=force_comm)
+                                  check=bsp_check, names=list(model.named_parameters()), force_comm=force_comm,
+                                  compress=grad_compress)
         if use_graph and self.dp.comm_on and not graph_comm:
             # a captured step holds the bucket all-reduces, the BN-statistics sync and their waits inside the graph
             # (RCCL collectives captured on the current stream, replayed every step): opt in with graph_comm=True -
@@ -373,6 +385,8 @@ class TrainStep:
                                                     images if isinstance(images, (list, tuple)) else [images])]
         micro = list(zip(images, labels)) if isinstance(images, (list, tuple)) else [(images, labels)]
         n = len(micro)
+        if self.dp.compress is not None:
+            self.dp.steps = self.global_step  # begin_step counts global steps (a resumed run included)
         losses = []
         if self.distill is not None:
             self._kl_rows = []

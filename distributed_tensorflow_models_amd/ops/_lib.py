@@ -119,6 +119,11 @@ _SIGS = {
     "dtm_multi_tensor_lamb": (_I, [_P, _P, _I, _P, _I, _D, _D, _D, _I, _P, _P, _P, _P, _P, _P, _P]),
     "dtm_check_finite": (None, [_P, _L, _P, _P]),
     "dtm_grad_accum": (_I, [_P, _P, _L, _I, _P, _P]),
+    "dtm_gc_chunk_size": (_I, []),
+    "dtm_gc_scratch_words": (_L, [_L]),
+    "dtm_grad_compress": (_I, [_P, _P, _L, _L, _P, _P, _P]),
+    "dtm_grad_compress_stages": (_I, [_P, _P, _L, _L, _P, _P, _I, _P]),
+    "dtm_grad_decompress": (_I, [_P, _L, _P, _I, _L, _P]),
     "dtm_sam_chunk_size": (_I, []),
     "dtm_sam_tensor_bytes": (_I, []),
     "dtm_sam_chunk_bytes": (_I, []),

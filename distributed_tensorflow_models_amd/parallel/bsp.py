@@ -31,6 +31,11 @@ Design (MI355X-first):
     last move their gradients into a second flat buffer of the same layout (one launch over the whole buffer, which
     also clears the flat one) and issue no collective; the last one adds the accumulator to each bucket right before
     that bucket's all-reduce (csrc/kernels/grad_accum.hip), so a step of N micro-batches costs the collectives of one.
+  * top-k sparsification with error feedback (``compress=GradCompress(ratio, begin_step)``, opt-in; ops/compress.py,
+    csrc/kernels/grad_compress.hip): a plain bucket sends the k largest-magnitude entries of residual + gradient as
+    one int32[2k] packet of indices and bit patterns, all-gathered where the all-reduce would be issued, and keeps
+    the rest in a rank-local residual; ``finish`` zeroes the bucket and adds the packets in rank order, so every
+    rank ends with the same bits.  With one rank the same function runs without the collective.
 With world_size == 1 no collective is issued.
 """
 import os
@@ -40,13 +45,34 @@ import torch.distributed as dist
 
 from ..ops import _lib
 from ..ops import accum as _accum
+from ..ops import compress as _compress
+from ..ops.compress import GradCompress  # noqa: F401  (BSPDataParallel(compress=GradCompress(...)))
 from ..ops import nn as opsnn
 from ..utils.profiler import roctx
 
 
 class BSPDataParallel:
     def __init__(self, params, bucket_mb=32.0, process_group=None, device=None, overlap=True, grad_dtype=torch.float32,
-                 comm_dtype=None, tail_mb=1.0, check=None, names=None, force_comm=False):
+                 comm_dtype=None, tail_mb=1.0, check=None, names=None, force_comm=False, compress=None):
+        # compress: an ops.compress.GradCompress - top-k sparsification with error feedback.  From step
+        # compress.begin_step on, every plain bucket sends the k largest-magnitude entries of residual + gradient as
+        # one int32[2k] packet (an all-gather in the all-reduce's place) and keeps the rest in ``res``, a rank-local
+        # buffer of the flat one's layout; ``finish`` rebuilds the bucket as the rank-order sum of the packets.
+        # Live-window compact buckets keep their dense all-reduce.  With one rank and no force_comm the same function
+        # runs without the collective.  None: nothing is constructed, today's launches and bits.
+        if compress is not None:
+            if not isinstance(compress, GradCompress):
+                raise ValueError("compress must be an ops.compress.GradCompress or None, got %r" % (compress,))
+            if grad_dtype != torch.float32 or (comm_dtype is not None and comm_dtype != grad_dtype):
+                raise ValueError("gradient compression sends fp32 values: it is not combined with a %s wire or %s "
+                                 "gradients" % (comm_dtype, grad_dtype))
+        self.compress = compress
+        self.res = None          # the residual: allocated when compression is first used, never communicated
+        self.steps = 0           # steps finished (compress.begin_step counts them)
+        self.packets = {}        # bucket index -> this rank's packet of the last compressed step
+        self.compress_hook = None  # optional callable(bucket index, start, end) right before a bucket is compressed
+        self._cbufs = {}         # bucket index -> (k, packet, gathered [W, 2k]); rebuilt with the buckets
+        self._cscratch = None
         self.params = [p for p in params if p.requires_grad]
         self.pg = process_group
         self.world = dist.get_world_size(process_group) if dist.is_available() and dist.is_initialized() else 1
@@ -162,6 +188,7 @@ class BSPDataParallel:
             self.contrib[p] = lst
         self._have = [0] * len(self.buckets)
         self._launched = [False] * len(self.buckets)
+        self._cbufs, self.packets = {}, {}  # (k is fixed while the buckets stand)
 
     def _on_live_window(self, p, win):
         """A conv announced its live-tap window (forward, before any bucket of this step launched)."""
@@ -172,12 +199,57 @@ class BSPDataParallel:
         self.windows[p] = win
         self._build_buckets()
 
-    def wire_elements(self):
-        """Gradient elements sent per all-reduce step (compact buckets count their window only)."""
-        n = 0
-        for bi, b in enumerate(self.buckets):
-            n += self.compact[bi][2].numel() if bi in self.compact else b[1] - b[0]
-        return n
+    def wire_elements(self, step=None):
+        """Gradient elements sent per all-reduce step (compact buckets count their window only; a compressed bucket
+        counts the 2k words of its packet).  ``step``: the step asked about (default: the one in progress or next)."""
+        return sum(self.bucket_elements(step))
+
+    # ---- top-k sparsification (ops/compress.py) ----------------------------------------------
+    def compressing(self, step=None):
+        """Whether step ``step`` (default: the one in progress or, between steps, the next) sends packets: a host
+        decision per step."""
+        return self.compress is not None and (self.steps if step is None else step) >= self.compress.begin_step
+
+    def _compress_bufs(self, bi):
+        """(k, packet, gathered) of plain bucket ``bi``; the residual and the scratch on first use."""
+        if self.res is None:
+            self.res = torch.zeros_like(self.flat)
+        if bi not in self._cbufs:
+            s, e = self.buckets[bi]
+            k = _compress.bucket_k(e - s, self.compress.ratio)
+            W = self.world if self.comm_on else 1
+            gathered = torch.zeros((W, 2 * k), dtype=torch.int32, device=self.flat.device)
+            # (no collective: the own packet is the gathered buffer's one row)
+            packet = torch.zeros(2 * k, dtype=torch.int32, device=self.flat.device) if self.comm_on else gathered[0]
+            self._cbufs[bi] = (k, packet, gathered)
+        if self.flat.is_cuda and self._cscratch is None:
+            words = max(_compress.scratch_words(b[1] - b[0]) for i, b in enumerate(self.buckets)
+                        if i not in self.compact)
+            self._cscratch = torch.zeros(words, dtype=torch.int32, device=self.flat.device)
+        return self._cbufs[bi]
+
+    def _compress_now(self, bi):
+        s, e = self.buckets[bi]
+        k, packet, gathered = self._compress_bufs(bi)
+        if self.compress_hook is not None:
+            self.compress_hook(bi, s, e)
+        _compress.compress_bucket(self.res[s:e], self.flat[s:e], k, packet, self._cscratch)
+        self.packets[bi] = packet
+        work = None
+        if self.comm_on:
+            if dist.get_backend(self.pg) == "nccl":
+                work = dist.all_gather_into_tensor(gathered.view(-1), packet, group=self.pg, async_op=True)
+            else:  # (gloo has no all_gather_into_tensor)
+                work = dist.all_gather(list(gathered.unbind(0)), packet, group=self.pg, async_op=True)
+        self._works.append((bi, work))
+
+    def residual_norm(self):
+        """2-norm of the residual (0 before compression is first used).  Reads the device: logged steps only."""
+        return 0.0 if self.res is None else float(torch.linalg.vector_norm(self.res))
+
+    def wire_bytes(self, step=None):
+        """Bytes this rank sends per step."""
+        return self.wire_elements(step) * torch.empty((), dtype=self.comm_dtype).element_size()
 
     def close(self):
         opsnn.remove_live_window_hook(self._win_hook)
@@ -305,7 +377,7 @@ class BSPDataParallel:
         if self._launched[bi]:
             return
         self._launched[bi] = True
-        if not self.comm_on:
+        if not self.comm_on and (not self.compressing() or bi in self.compact):
             return
         side = _lib.side_active() if self.flat.is_cuda else None
         if side is not None and torch.cuda.current_stream() != side:
@@ -329,6 +401,10 @@ class BSPDataParallel:
             else:
                 s, e = self.buckets[bi]
                 self._fold(s, e)  # after every write of the bucket on both streams, before the wire cast
+                if self.compressing():
+                    with roctx("compress_bucket_%d" % bi):
+                        self._compress_now(bi)  # in the fold's place in stream order; an all-gather for the all-reduce
+                    return
                 buf = self.flat[s:e]
                 if self.comm is not None:
                     buf = self.comm[s:e]
@@ -347,10 +423,20 @@ class BSPDataParallel:
         if self.flat.is_cuda:
             _lib.side_join()
         if not self.comm_on:
-            self._fold(0, self.flat.numel())  # no collective, no per-bucket launch: one fold over the buffer
+            if self.compressing():  # the plain buckets were folded in front of their compress launches
+                for p, _win, _buf, _low in self.compact.values():
+                    self._fold(self.offsets[p], self.offsets[p] + p.numel())
+            else:
+                self._fold(0, self.flat.numel())  # no collective, no per-bucket launch: one fold over the buffer
         for bi, w in self._works:
-            w.wait()
-            if bi in self.compact:
+            if w is not None:
+                w.wait()
+            if bi in self._cbufs and bi not in self.compact and self.compressing():
+                s, e = self.buckets[bi]
+                k, _packet, gathered = self._cbufs[bi]
+                with roctx("decompress_bucket_%d" % bi):
+                    _compress.decompress_bucket(self.flat[s:e], gathered, k)  # the rank-order sum of the packets
+            elif bi in self.compact:
                 p, (r0, r1, s0, s1), buf, low = self.compact[bi]
                 p.main_grad[:, r0:r1, s0:s1, :].copy_(low if low is not None else buf)  # scatter back
             elif self.comm is not None:
@@ -359,12 +445,15 @@ class BSPDataParallel:
         if self.check:
             # nothing may write a gradient between the waits above and the next zero_grad
             self._seen = set(self.contrib)
-        self._done_works = self._works
+        self._done_works = [(bi, w) for bi, w in self._works if w is not None]
         self._works = []
+        self.steps += 1
 
-    def bucket_elements(self):
-        """Elements each bucket sends, in bucket order."""
-        return [self.compact[bi][2].numel() if bi in self.compact else b[1] - b[0]
+    def bucket_elements(self, step=None):
+        """Elements (32-bit words for a compressed bucket: 2k) each bucket sends, in bucket order."""
+        comp = self.compressing(step)
+        return [self.compact[bi][2].numel() if bi in self.compact
+                else (2 * _compress.bucket_k(b[1] - b[0], self.compress.ratio) if comp else b[1] - b[0])
                 for bi, b in enumerate(self.buckets)]
 
     def bucket_ms(self):

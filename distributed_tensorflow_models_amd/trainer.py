@@ -178,6 +178,33 @@ def sam_config(FLAGS, mode):
     return SamConfig(rho, bool(FLAGS.sam_adaptive))
 
 
+COMPRESS_BSP_ONLY = ("--grad_compress_ratio needs --sync_mode bsp (got %s): under asp / ssp a worker pushes to the "
+                     "parameter store, and a residual kept on the worker would be applied against weights it no "
+                     "longer matches")
+COMPRESS_NO_BF16 = ("--grad_compress_ratio and --grad_comm_dtype bf16 are not combined: a packet carries fp32 bit "
+                    "patterns")
+COMPRESS_NO_GRAPH = ("--grad_compress_ratio and --use_hipgraph are not combined: the dense warm-up is a host decision "
+                     "per step")
+
+
+def compress_config(FLAGS, mode):
+    """The GradCompress of --grad_compress_ratio / --grad_compress_begin_step, or None with a ratio of 0 (checked
+    before any process group exists)."""
+    ratio = float(FLAGS.grad_compress_ratio)
+    if ratio == 0.0:
+        if FLAGS.grad_compress_begin_step:
+            raise ValueError("--grad_compress_begin_step needs --grad_compress_ratio")
+        return None
+    if mode in ("asp", "ssp"):
+        raise ValueError(COMPRESS_BSP_ONLY % mode)
+    if FLAGS.grad_comm_dtype == "bf16":
+        raise ValueError(COMPRESS_NO_BF16)
+    if FLAGS.use_hipgraph:
+        raise ValueError(COMPRESS_NO_GRAPH)
+    from .ops.compress import GradCompress
+    return GradCompress(ratio, FLAGS.grad_compress_begin_step)  # (its own checks: a ratio in (0, 1], a step >= 0)
+
+
 def parse_model_kw(text):
     """"k=v,..." -> {k: int or float}: the numeric model keywords of --distill_teacher_kw."""
     out = {}
@@ -293,6 +320,10 @@ def define_common_flags(flags, preset):
             ("bn_sync_every", I, 1, "BSP: average the BN moving statistics over the replicas every N steps"),
             ("rccl_channels", I, 0, "pin the RCCL channel count (0 = RCCL's choice)"),
             ("grad_comm_dtype", S, "fp32", "gradient all-reduce dtype on the wire: fp32 | bf16"),
+            # top-k sparsification with error feedback (ops.compress.GradCompress; BSP only)
+            ("grad_compress_ratio", Fl, 0.0, "send only this fraction of every gradient bucket, its largest-magnitude "
+             "entries of residual + gradient, and keep the rest for the next step, in (0, 1] (0 = off)"),
+            ("grad_compress_begin_step", I, 0, "global steps before this one use the dense all-reduce"),
             ("deterministic", B, False, "bit-reproducible GPU reductions (no cross-block fp32 atomics)"),
             ("trace_steps", S, "", "a:b -> export a Chrome trace of steps [a, b)"),
             ("fresh", B, False, "wipe train_dir before training (the reference always did)"),
@@ -406,6 +437,7 @@ def train(preset, flags, default_mode="bsp"):
                             FLAGS.mix_per_row, seed=FLAGS.seed)
     prune_cfg = prune_config(FLAGS, mode)
     sam_cfg = sam_config(FLAGS, mode)
+    compress_cfg = compress_config(FLAGS, mode)
     distill_ckpt = distill_kw = None
     if FLAGS.distill_teacher:
         if mode in ("asp", "ssp"):
@@ -533,7 +565,8 @@ def train(preset, flags, default_mode="bsp"):
                             else None, lars_eeta=FLAGS.lars_eeta, lars_epsilon=FLAGS.lars_epsilon,
                             clip_global_norm=FLAGS.clip_global_norm if FLAGS.clip_global_norm > 0 else None,
                             beta1=FLAGS.adam_beta1, beta2=FLAGS.adam_beta2, accum_steps=accum, mix=mix_cfg, rank=rank,
-                            distill=distill_cfg, prune=prune_cfg, sam=sam_cfg, **opt_kw)
+                            distill=distill_cfg, prune=prune_cfg, sam=sam_cfg, grad_compress=compress_cfg,
+                            **opt_kw)
         # (the pruner's <scope>/mask and <scope>/threshold in front of the global step, which stays last)
         vars_ = model_variables(model, step_fn.opt, gstep, pruner=step_fn.pruner, **ckpt_kw)
         vars_[-1].name = cfg.get("global_step_name", "global_step")
@@ -706,6 +739,10 @@ def train(preset, flags, default_mode="bsp"):
                 extra["distill_kl"] = step_fn.last_distill_kl()  # a device read, after the synchronisation above
             if sam_cfg is not None and metrics.f is not None:
                 extra["sam_grad_norm"] = step_fn.last_sam_norm()  # a device read, after the synchronisation above
+            if compress_cfg is not None and metrics.f is not None:
+                extra["grad_compress_ratio"] = compress_cfg.ratio
+                extra["wire_mb"] = step_fn.dp.wire_bytes(gs - 1) / 1e6  # sent per rank in the step just run
+                extra["residual_norm"] = step_fn.dp.residual_norm()  # a device read, after the synchronisation above
             if prune_cfg is not None and metrics.f is not None:
                 # a device read, after the synchronisation above
                 extra["sparsity"], extra["prune_target"] = step_fn.last_sparsity()

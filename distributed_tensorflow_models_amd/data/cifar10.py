@@ -109,13 +109,21 @@ def _augment_torch(images_u8, S, p, dtype):
 
 
 class Cifar10Input:
-    """distorted_inputs(batch) / inputs(eval) with a native prefetching reader."""
+    """distorted_inputs(batch) / inputs(eval) with a native prefetching reader.
+
+    randaugment: a RandAugmentConfig (ops/randaugment.py) applied uint8 -> uint8 to the raw 32 x 32 training batch in
+    front of ``augment`` (None, or 0 layers, or eval data: no object, buffer or launch of it exists).  The plan of a
+    batch is sample_plan(cfg, rank, batch index, ...); the batch index counts this object's training batches from 0,
+    in a resumed run too."""
 
     def __init__(self, data_dir, batch_size, image_size=32, eval_data=False, device="cpu", shuffle=True, seed=0,
-                 nslots=4, synthetic_if_missing=True):
+                 nslots=4, synthetic_if_missing=True, randaugment=None, rank=0):
         self.batch_size, self.image_size, self.eval_data = batch_size, image_size, eval_data
         self.device = torch.device(device)
         self.rng = np.random.RandomState(seed)
+        self.randaugment = randaugment if (randaugment is not None and randaugment.layers > 0
+                                           and not eval_data) else None
+        self.rank, self.batch_index = int(rank), 0
         files = data_files(data_dir or "", eval_data)
         self.native = None
         self.synthetic = False
@@ -167,6 +175,12 @@ class Cifar10Input:
 
     def next_batch(self):
         img, lab = self._raw_batch()
+        if self.randaugment is not None:
+            from ..ops import randaugment as ra
+            B, H, W, _C = img.shape
+            plan = ra.sample_plan(self.randaugment, self.rank, self.batch_index, B, H, W)
+            self.batch_index += 1
+            img = ra.randaugment(img.contiguous(), plan.to(img.device))
         dtype = torch.bfloat16 if self.device.type == "cuda" else torch.float32
         return augment(img, self.image_size, distort=not self.eval_data, rng=self.rng, dtype=dtype), lab
 

@@ -278,8 +278,12 @@ class BatchInputs:
     """num_readers x num_preprocess_threads pipeline producing (images [B,S,S,3], labels [B])."""
 
     def __init__(self, dataset, batch_size, train=True, image_size=299, num_preprocess_threads=4, num_readers=4,
-                 queue_batches=4, seed=0, device="cpu", shuffle_buffer=1024):
+                 queue_batches=4, seed=0, device="cpu", shuffle_buffer=1024, randaugment=None, rank=0):
         self.files = dataset.data_files()
+        # RandAugment on training batches (a RandAugmentConfig of ops/randaugment.py; None or 0 layers: off), the
+        # same call as the device pipeline's, on the CPU batch; the batch index restarts at 0 in a resumed run
+        self.randaugment = randaugment if (randaugment is not None and randaugment.layers > 0 and train) else None
+        self.rank, self.batch_index = int(rank), 0
         self.B, self.S, self.train, self.device = batch_size, image_size, train, torch.device(device)
         self.records = queue.Queue(maxsize=shuffle_buffer)
         self.examples = queue.Queue(maxsize=batch_size * queue_batches)
@@ -338,6 +342,12 @@ class BatchInputs:
         xs, ys = zip(*got)
         x = torch.from_numpy(np.stack(xs))
         y = torch.tensor(ys, dtype=torch.int64)
+        if self.randaugment is not None:
+            from ..ops import randaugment as ra
+            plan = ra.sample_plan(self.randaugment, self.rank, self.batch_index, self.B, self.S, self.S)
+            self.batch_index += 1
+            # [-1, 1] -> 8-bit pixels -> the ops -> [-1, 1]: the affine pairs of the device pipeline
+            x = ra.randaugment(x, plan, out_kind="float32", in_affine=(0.5, 0.5), out_affine=(2.0 / 255.0, -1.0))
         if self.device.type == "cuda":
             x = x.pin_memory().to(self.device, non_blocking=True).to(torch.bfloat16)
             y = y.to(self.device, non_blocking=True)

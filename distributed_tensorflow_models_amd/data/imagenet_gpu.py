@@ -316,11 +316,29 @@ def pack_batch(images, params, out=None):
     return buf, tab
 
 
-def gpu_preprocess(images, params, size, device, out_dtype=torch.bfloat16):
-    """Run the HIP preprocessing on host-decoded images with given parameters -> [B, size, size, 3]."""
+# RandAugment behind the prep (ops/randaugment.py): the prep's [-1, 1] fp32 output is read as 8-bit pixels,
+# q((y * 0.5 + 0.5) * 255), and the last layer writes v * (2 / 255) - 1 in the model's type.  The 8-bit quantisation
+# is part of the recipe: RandAugment is defined on uint8 images.
+RA_IN_AFFINE = (0.5, 0.5)
+RA_OUT_AFFINE = (2.0 / 255.0, -1.0)
+
+
+def _randaugment_prepped(x32, plan, out_dtype):
+    from ..ops import randaugment as ra
+    return ra.randaugment(x32, plan.to(x32.device), out_kind=out_dtype, in_affine=RA_IN_AFFINE,
+                          out_affine=RA_OUT_AFFINE)
+
+
+def gpu_preprocess(images, params, size, device, out_dtype=torch.bfloat16, randaugment=None):
+    """Run the HIP preprocessing on host-decoded images with given parameters -> [B, size, size, 3].
+    randaugment: a RandAugmentPlan for [B, size, size] applied behind the prep (the prep then writes fp32)."""
     L = _lib.lib()
     assert L.dtm_prep_params_bytes() == _PARAM_DT.itemsize
     buf, tab = pack_batch(images, params)
+    if randaugment is not None:
+        x32, _stage = _launch(torch.from_numpy(buf), torch.from_numpy(tab.view(np.uint8)), len(images), size, device,
+                              torch.float32)
+        return _randaugment_prepped(x32, randaugment, out_dtype), _stage
     return _launch(torch.from_numpy(buf), torch.from_numpy(tab.view(np.uint8)), len(images), size, device,
                    out_dtype)
 
@@ -345,8 +363,13 @@ class GPUBatchInputs:
 
     def __init__(self, dataset, batch_size, train=True, image_size=299, num_preprocess_threads=4, num_readers=4,
                  num_decoders=8, seed=0, device="cuda", shuffle_buffer=1024, prefetch=2, decode_processes=None,
-                 split_decode=None, shm_kw=None):
+                 split_decode=None, shm_kw=None, randaugment=None, rank=0):
         self.files = dataset.data_files()
+        # RandAugment on training batches (a RandAugmentConfig; None or 0 layers: no object, buffer or launch of it
+        # exists): plan = sample_plan(cfg, rank, batch index, ...), the index counted from 0 by this object, in a
+        # resumed run too
+        self.randaugment = randaugment if (randaugment is not None and randaugment.layers > 0 and train) else None
+        self.rank, self.batch_index = int(rank), 0
         # split JPEG decode (host Huffman + device IDCT / colour, data/jpeg.py; bit-exact with PIL): opt-in
         # (DTM_SPLIT_DECODE=1).  Measured on one MI355X box with 16 decoder processes
         # (profiles/r3/r3_imagenet_pipeline_split_vs_full.log): full host decode 12.2-13.6k img/s, split
@@ -640,7 +663,14 @@ class GPUBatchInputs:
         bt, tt, lab, split = item
         if split is not None:
             bt = self._device_decode(bt, split)
-        x, self._stage = _launch(bt, tt, self.B, self.S, self.device, torch.bfloat16, self._stage)
+        if self.randaugment is not None:
+            from ..ops import randaugment as ra
+            x32, self._stage = _launch(bt, tt, self.B, self.S, self.device, torch.float32, self._stage)
+            plan = ra.sample_plan(self.randaugment, self.rank, self.batch_index, self.B, self.S, self.S)
+            self.batch_index += 1
+            x = _randaugment_prepped(x32, plan, torch.bfloat16)
+        else:
+            x, self._stage = _launch(bt, tt, self.B, self.S, self.device, torch.bfloat16, self._stage)
         self.images_done += self.B
         return x, lab.to(self.device, non_blocking=True)
 

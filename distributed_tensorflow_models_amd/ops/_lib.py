@@ -106,6 +106,7 @@ _SIGS = {
     "dtm_softmax_xent_mix": (_I, [_P, _I, _P, _P, _P, _P, _I, _I, _F, _F, _I, _P]),
     "dtm_softmax_xent_distill": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _I, _F, _F, _F, _F, _I, _P]),
     "dtm_mix_images":(_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "dtm_randaugment": (_I, [_P, _I, _F, _F, _P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _F, _F, _P]),
     "dtm_opt_chunk_size": (_I, []),
     "dtm_opt_tensor_bytes": (_I, []),
     "dtm_opt_chunk_bytes": (_I, []),

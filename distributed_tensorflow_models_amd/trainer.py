@@ -134,6 +134,25 @@ PRUNE_BSP_ONLY = ("--prune_sparsity needs --sync_mode bsp (got %s): the masks ag
                   "communication only because every rank holds the same weight bits, which asp / ssp do not give")
 
 
+RANDAUGMENT_NEEDS_IMAGES = ("--randaugment_layers needs a dataset of uint8 images (cifar10, imagenet), got %s: the "
+                            "synthetic batches are random floats with nothing to augment")
+
+
+def randaugment_config(FLAGS, cfg):
+    """The RandAugmentConfig of the --randaugment_* flags, or None with --randaugment_layers 0 (checked before any
+    process group exists).  Input-side only, so it works under bsp, asp and ssp alike; the seed is --seed."""
+    if not FLAGS.randaugment_layers:
+        return None
+    from .ops.randaugment import RandAugmentConfig
+    ra = RandAugmentConfig(FLAGS.randaugment_layers, FLAGS.randaugment_magnitude, FLAGS.randaugment_prob,
+                           FLAGS.randaugment_ops or None, FLAGS.randaugment_translate_ratio,
+                           FLAGS.randaugment_cutout_ratio, seed=FLAGS.seed)
+    ds = "synthetic_imagenet" if FLAGS.synthetic_data and cfg["dataset"] == "imagenet" else cfg["dataset"]
+    if ds not in ("cifar10", "imagenet"):
+        raise ValueError(RANDAUGMENT_NEEDS_IMAGES % ds)
+    return ra
+
+
 def prune_config(FLAGS, mode):
     """The PruneConfig of the --prune_* flags, or None with --prune_sparsity 0 (checked before any process group
     exists).  --prune_exclude is a regular expression searched in a variable's TF name."""
@@ -287,6 +306,16 @@ def define_common_flags(flags, preset):
             ("mix_prob", Fl, 1.0, "probability that a batch (a row with --mix_per_row) is mixed at all"),
             ("mix_switch_prob", Fl, 0.5, "with both alphas above 0: the probability of CutMix over mixup"),
             ("mix_per_row", B, False, "draw kind, weight and box per row instead of per batch"),
+            # RandAugment in the input pipelines (ops/randaugment.py; every sync mode; the sampler's seed is --seed)
+            ("randaugment_layers", I, 0, "RandAugment: ops applied per training image (0 = off)"),
+            ("randaugment_magnitude", Fl, 9.0, "RandAugment: the magnitude, in [0, 10]"),
+            ("randaugment_prob", Fl, 1.0, "RandAugment: probability that a drawn op is applied (else the identity)"),
+            ("randaugment_ops", S, "", "RandAugment: comma-separated op names ('' = the 14 default ops; Invert, "
+             "SolarizeAdd and Cutout are available by name)"),
+            ("randaugment_translate_ratio", Fl, 0.45, "RandAugment: translation at magnitude 10, as a fraction of the "
+             "image side"),
+            ("randaugment_cutout_ratio", Fl, 0.18, "RandAugment: half side of the Cutout box at magnitude 10, as a "
+             "fraction of the shorter image side"),
             # knowledge distillation (engine.DistillConfig; BSP only)
             ("distill_teacher", S, "", "nets_factory name of a frozen teacher network, built with the student's "
              "number of classes ('' = off)"),
@@ -349,12 +378,15 @@ def _device():
     return torch.device("cpu")
 
 
-def make_input(cfg, batch_size, device, flags, rank):
+def make_input(cfg, batch_size, device, flags, rank, randaugment=None):
+    """The training input of ``cfg``'s dataset.  randaugment: a RandAugmentConfig for the pipelines that hold uint8
+    images (None: the calls, launches and bits of a run without it)."""
     ds = "synthetic_imagenet" if flags.synthetic_data and cfg["dataset"] == "imagenet" else cfg["dataset"]
     S = cfg["image_size"]
+    ra_kw = dict(randaugment=randaugment, rank=rank) if randaugment is not None else {}
     if ds == "cifar10":
         from .data import cifar10
-        return cifar10.distorted_inputs(flags.data_dir, batch_size, S, device=device, seed=flags.seed + rank)
+        return cifar10.distorted_inputs(flags.data_dir, batch_size, S, device=device, seed=flags.seed + rank, **ra_kw)
     if ds == "synthetic_mnist":
         from .data.synthetic import synthetic_mnist
 
@@ -379,9 +411,9 @@ def make_input(cfg, batch_size, device, flags, rank):
             capacity.decode_capacity_check(cfg["model"], mode=split, log=logging.warning)
             return imagenet_gpu.distorted_inputs(imagenet.ImagenetData("train", flags.data_dir), batch_size,
                                                  image_size=S, device=device, seed=flags.seed + rank,
-                                                 split_decode=split)
+                                                 split_decode=split, **ra_kw)
         return imagenet.distorted_inputs(imagenet.ImagenetData("train", flags.data_dir), batch_size, image_size=S,
-                                         device=device, seed=flags.seed + rank)
+                                         device=device, seed=flags.seed + rank, **ra_kw)
     from .data.synthetic import SyntheticImages
     return SyntheticImages(batch_size, S, S, 3, cfg["num_classes"], device, seed=flags.seed + rank,
                            label_offset=1 if cfg["num_classes"] == 1001 else 0)
@@ -435,6 +467,7 @@ def train(preset, flags, default_mode="bsp"):
         from .ops.mix import MixConfig
         mix_cfg = MixConfig(FLAGS.mixup_alpha, FLAGS.cutmix_alpha, FLAGS.mix_prob, FLAGS.mix_switch_prob,
                             FLAGS.mix_per_row, seed=FLAGS.seed)
+    ra_cfg = randaugment_config(FLAGS, cfg)
     prune_cfg = prune_config(FLAGS, mode)
     sam_cfg = sam_config(FLAGS, mode)
     compress_cfg = compress_config(FLAGS, mode)
@@ -493,7 +526,7 @@ def train(preset, flags, default_mode="bsp"):
             if p.requires_grad:
                 p.weight_decay = cfg["wd_all"]
     B = FLAGS.batch_size
-    data = make_input(cfg, B, device, FLAGS, rank)
+    data = make_input(cfg, B, device, FLAGS, rank, ra_cfg)
 
     # ---- schedule (C16, C19) ---------------------------------------------------------------------
     n_train = CIFAR_TRAIN if cfg["dataset"] in ("cifar10",) else IMAGENET_TRAIN
@@ -735,6 +768,8 @@ def train(preset, flags, default_mode="bsp"):
                 extra["adam_step"] = step_fn.opt.adam_step()  # applied updates: lags global_step after a NaN skip
             if mix_cfg is not None and metrics.f is not None:
                 extra["mix_lambda"] = step_fn.last_mix_lambda()  # mean own-label weight of this step (a host value)
+            if ra_cfg is not None and metrics.f is not None:
+                extra["randaugment_layers"], extra["randaugment_magnitude"] = ra_cfg.layers, ra_cfg.magnitude
             if distill_cfg is not None and metrics.f is not None:
                 extra["distill_kl"] = step_fn.last_distill_kl()  # a device read, after the synchronisation above
             if sam_cfg is not None and metrics.f is not None:
@@ -766,7 +801,7 @@ def train(preset, flags, default_mode="bsp"):
         # every worker runs the probe, as every reference worker does (resnet/cifar10_resnet_bsp.py:146-148)
         if FLAGS.train_accuracy_every and step % FLAGS.train_accuracy_every == 0:
             if probe is None:
-                probe = make_input(cfg, FLAGS.train_accuracy_batch, device, FLAGS, rank + 7919)
+                probe = make_input(cfg, FLAGS.train_accuracy_batch, device, FLAGS, rank + 7919, ra_cfg)
             acc = train_accuracy_probe(model, probe)
             # tf.logging.info('evaluation: step - '+str(step)+'; accuracy: '+ str(accuracy))
             logging.info("evaluation: step - %d; accuracy: %s", step, str(np.float32(acc)))

@@ -31,6 +31,8 @@ Same variables, names and arithmetic (checkpoints interchange); differences of t
 
 * a batch with a NaN or +-Inf element leaves the range variables untouched and is counted (``nonfinite_batches``)
   instead of poisoning them for the rest of the run;
+* ``QuantConfig(integer=True)`` (evaluation only): every quantised activation carries its uint8 codes (``y.q8``) and
+  a layer whose input carries them runs in integer arithmetic on them (``ops/int8.py``, ``compat/slim.py``);
 * the weight quantiser tracks its last-value range before the delay too (the unfused one starts at the delay), and
   with ``is_training=False`` it reads the recorded range as TF's eval graph does (the unfused one recomputes it from
   the weights).
@@ -39,7 +41,11 @@ import torch
 
 
 class QuantConfig:
-    def __init__(self, quant_delay=0, num_bits=8, ema_decay=0.999, is_training=True, fold_bn=True, fused=False):
+    def __init__(self, quant_delay=0, num_bits=8, ema_decay=0.999, is_training=True, fold_bn=True, fused=False,
+                 integer=False):
+        if integer and (not fused or is_training or int(num_bits) != 8):
+            raise ValueError("QuantConfig(integer=True) needs fused=True, is_training=False and num_bits=8")
+        self.integer = bool(integer)  # evaluation in 8-bit integer arithmetic where a layer allows it (ops/int8.py)
         self.fused = bool(fused)  # quantisers as device passes with device-side state (ops/fakequant.py)
         self._counter = None      # fused: int64 device count of training forwards (what ``step`` counts on the host)
         self.fold_bn = bool(fold_bn)  # fold slim.batch_norm into the producing conv's weights (TF default)
@@ -135,13 +141,33 @@ def quantize_weights(w, var_fn, cfg):
     return fake_quant(w, vmin.detach(), vmax.detach(), cfg.num_bits, narrow=True)
 
 
+def frozen_state(prefix, var_fn, cfg, narrow):
+    """Integer evaluation: the QuantizerState of the layer scope's ``<prefix>/min|max`` quantiser with its record
+    written from the stored range (once per weights version: a restore moves the range variables)."""
+    from ..ops import fakequant as FQ
+    from ..ops.nn import WEIGHT_VERSION
+    vmin = var_fn(prefix + "/min", 0.0)
+    vmax = var_fn(prefix + "/max", 0.0 if narrow else 6.0)
+    st = FQ.state_of(vmin)
+    if getattr(st, "frozen_version", None) != WEIGHT_VERSION[0]:
+        FQ.finalize(vmin.data, vmin, vmax, st, cfg.counter(vmin.device), FQ.FROZEN, cfg.ema_decay, cfg.num_bits, narrow,
+                    cfg.quant_delay, cfg.is_training)
+        st.frozen_version = WEIGHT_VERSION[0]
+    return st
+
+
 def quantize_activations(y, var_fn, cfg, training):
     vmin = var_fn("act_quant/min", 0.0)
     vmax = var_fn("act_quant/max", 6.0)
     if cfg.fused:
         from ..ops import fakequant as FQ
-        return FQ.quantize(y, vmin, vmax, cfg, FQ.ACT_TRAIN if (training and cfg.is_training) else FQ.FROZEN,
-                           narrow=False)
+        yq = FQ.quantize(y, vmin, vmax, cfg, FQ.ACT_TRAIN if (training and cfg.is_training) else FQ.FROZEN,
+                         narrow=False)
+        if cfg.integer and y.numel():  # the entry into the integer domain: the codes of the same quantiser
+            from ..ops import int8
+            st = FQ.state_of(vmin)
+            yq.q8 = (int8.quantize_u8(y, st.rec), st)
+        return yq
     if training and cfg.is_training:
         with torch.no_grad():
             d = cfg.ema_decay

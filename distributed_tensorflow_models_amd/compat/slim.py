@@ -352,8 +352,53 @@ def _qw(w):
 def _qa(y):
     if _store.quant is None:
         return y
+    if _store.quant.integer and getattr(y, "q8", None) is not None:
+        return y  # an integer layer's result: already this quantiser's codes and their dequantised values
     from . import quantize as Q
     return Q.quantize_activations(as_tensor(y), _qvar, _store.quant, _store.training)
+
+
+def _q8_act(fn):
+    """The name of an activation the integer layers fuse, else None."""
+    if fn is None:
+        return "none"
+    if fn in (torch.relu, E.relu, "relu"):
+        return "relu"
+    if fn in (E.relu6, "relu6") or getattr(fn, "__name__", "") in ("relu6", "_relu6"):
+        return "relu6"
+    return None
+
+
+def _q8_in(x, activation_fn):
+    """QuantConfig(integer=True): the (codes, quantiser state) an activation carries, when the layer's activation
+    function lets it run in integers on them; else None (the layer takes the float path on the dequantised values)."""
+    q = _store.quant
+    if q is None or not q.integer or _q8_act(activation_fn) is None:
+        return None
+    return getattr(x, "q8", None)
+
+
+def _q8_layer(q8, dtype, w, build, depthwise, stride, padding, activation_fn, wscope=None):
+    """One integer layer (ops/int8.py) inside the layer's scope.  ``build()`` -> (folded fp32 weights, fp32 bias): run
+    once per weights version, the prepared weights live on the parameter ``w``.  Returns the dequantised result with
+    its codes attached as ``.q8``."""
+    from . import quantize as Q
+    from ..ops import int8
+    cfg = _store.quant
+
+    def prepare():
+        wf, bias = build()
+        with variable_scope(wscope) if wscope else contextlib.nullcontext():
+            wst = Q.frozen_state("weights_quant", _qvar, cfg, narrow=True)
+        return int8.prepare_weights(wf.detach(), wst.rec, depthwise), bias.detach().float().contiguous()
+
+    with torch.no_grad():
+        qw, bias = int8.cached(w, prepare)
+        ost = Q.frozen_state("act_quant", _qvar, cfg, narrow=False)
+        fn = int8.depthwise_q8 if depthwise else int8.conv2d_q8
+        codes, y = fn(q8[0], q8[1].rec, qw, bias, ost.rec, stride, padding, _q8_act(activation_fn), dtype)
+    y.q8 = (codes, ost)
+    return y
 
 
 def _act(x, fn):
@@ -411,6 +456,15 @@ def _folded_bn(fold, gamma, beta, mm, mv, is_training, decay, epsilon, activatio
     quantisation is off; eval: the same with the moving mean / variance."""
     conv_fn, w, scale_fn = fold[:3]
     qscope = fold[3] if len(fold) > 3 else None
+    q8l = fold[4] if len(fold) > 4 else None  # (input, depthwise, stride, padding) of a layer the integer path covers
+    if not is_training and q8l is not None and _q8_in(q8l[0], activation_fn) is not None:
+        def build():
+            mult = torch.rsqrt(mv.detach() + epsilon)
+            if gamma is not None:
+                mult = mult * gamma
+            bias = -mm.detach() * mult
+            return scale_fn(w, mult), (bias + beta if beta is not None else bias)
+        return _q8_layer(q8l[0].q8, q8l[0].dtype, w, build, q8l[1], q8l[2], q8l[3], activation_fn, qscope)
     if is_training:
         y0 = as_tensor(conv_fn(w)).float()
         dims = tuple(range(y0.dim() - 1))
@@ -493,9 +547,13 @@ def conv2d(inputs, num_outputs, kernel_size, stride=1, padding="SAME", data_form
                          trainable=trainable)
         if normalizer_fn is not None and _fold_ok(normalizer_fn):
             fold = (lambda wt: F.conv2d(x, wt, None, stride, padding, dilation=rate), w,
-                    lambda wt, m: wt * m.reshape(-1, 1, 1, 1))
+                    lambda wt, m: wt * m.reshape(-1, 1, 1, 1), None,
+                    (x, False, stride, padding) if rate == 1 else None)
             return _qa(normalizer_fn(num_outputs, activation_fn=activation_fn, _fold=fold,
                                      **(normalizer_params or {})))
+        if normalizer_fn is None and rate == 1 and _q8_in(x, activation_fn) is not None:
+            return _q8_layer(x.q8, x.dtype, w, lambda: (w, b if b is not None else w.new_zeros(num_outputs)), False,
+                             stride, padding, activation_fn)
         fuse = normalizer_fn is None and activation_fn in (torch.relu, E.relu, "relu")
         y = F.conv2d(x, _qw(w), b, stride, padding, relu=fuse, dilation=rate)
         if normalizer_fn is not None:
@@ -550,7 +608,8 @@ def separable_conv2d(inputs, num_outputs, kernel_size, depth_multiplier=1, strid
         if num_outputs is None and normalizer_fn is not None and _fold_ok(normalizer_fn):
             # depthwise-only layer (MobileNet v1): BN folded into the depthwise weights per channel
             fold = (lambda wt: depthwise_conv2d(x, wt, stride, padding, rate), dw,
-                    lambda wt, m: wt * m.reshape(1, 1, cin, depth_multiplier), "depthwise_weights_q")
+                    lambda wt, m: wt * m.reshape(1, 1, cin, depth_multiplier), "depthwise_weights_q",
+                    (x, True, stride, padding) if rate == 1 and depth_multiplier == 1 else None)
             return _qa(normalizer_fn(cin * depth_multiplier, activation_fn=activation_fn, _fold=fold,
                                      **(normalizer_params or {})))
         if _store.quant is not None:
@@ -586,6 +645,7 @@ def fully_connected(inputs, num_outputs, activation_fn=torch.relu, normalizer_fn
                     biases_regularizer=None, reuse=None, trainable=True, scope=None, outputs_collections=None,
                     variables_collections=None):
     x = as_tensor(inputs)
+    q8 = _q8_in(x, activation_fn) if normalizer_fn is None else None
     x = x.reshape(x.shape[0], -1)
     with variable_scope(scope, "fully_connected", reuse=reuse):
         w = variable("weights", (x.shape[-1], num_outputs), initializer=weights_initializer,
@@ -594,6 +654,15 @@ def fully_connected(inputs, num_outputs, activation_fn=torch.relu, normalizer_fn
         if normalizer_fn is None and biases_initializer is not None:
             b = variable("biases", (num_outputs,), initializer=biases_initializer, regularizer=biases_regularizer,
                          trainable=trainable)
+        if q8 is not None:  # a 1x1 conv over [N,1,1,C]
+            n, cin = x.shape
+            y = _q8_layer((q8[0].reshape(n, 1, 1, cin), q8[1]), x.dtype, w,
+                          lambda: (w.t().reshape(num_outputs, 1, 1, cin),
+                                   b if b is not None else w.new_zeros(num_outputs)),
+                          False, 1, "VALID", activation_fn)
+            y2 = y.reshape(n, num_outputs)
+            y2.q8 = (y.q8[0].reshape(n, num_outputs), y.q8[1])
+            return y2
         fuse = normalizer_fn is None and activation_fn in (torch.relu, E.relu, "relu")
         y = F.linear(x, _qw(w), b, relu=fuse)
         if normalizer_fn is not None:

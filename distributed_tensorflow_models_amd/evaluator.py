@@ -176,6 +176,8 @@ def _write_extras(F, writer, jsonl, res, gs, p1, r5):
         if res["confusion"].shape[0] <= 512:  # larger matrices are saved, not drawn
             writer.add_image("Confusion matrix", _confusion_image(res["confusion"]), gs)
     # (eval_*: the printed values, over num_iter * batch_size; precision_at_1 / recall_at_k: over the valid rows)
+    if "int8_layers" in res:
+        scalars["int8_layers"] = res["int8_layers"]
     jsonl.write(global_step=gs, eval_precision_at_1=p1, eval_recall_at_5=r5, **scalars)
 
 
@@ -189,7 +191,10 @@ def evaluate(preset, flags):
         kw["depth_multiplier"] = F.depth_multiplier
     if "quantize" in F and F.quantize:  # create_eval_graph (mobilenet_v1_eval.py:126-127)
         from .compat.quantize import QuantConfig
-        kw["quantize"] = QuantConfig(is_training=False, fused=bool("quant_fused" in F and F.quant_fused))
+        int8_on = bool("quant_int8" in F and F.quant_int8)  # integer arithmetic (ops/int8.py); implies the fused path
+        kw["quantize"] = QuantConfig(is_training=False, fused=int8_on or bool("quant_fused" in F and F.quant_fused),
+                                     integer=int8_on)
+    int8_on = getattr(kw.get("quantize"), "integer", False)
     model = trainer.build_model_for_eval(preset, **kw).to(device)
     model.eval()
     if os.path.isdir(F.eval_dir):
@@ -211,8 +216,14 @@ def evaluate(preset, flags):
             restore_for_eval(model, path, F.use_ema, prefix=cfg.get("scope_prefix", ""))
             gs = step_from_path(path)
             t0 = time.time()
+            if int8_on:
+                from .ops import int8
+                int8.reset_layers()
             p1, r5, res = _eval_once(model, data, F.num_examples, F.batch_size, confusion=F.eval_confusion)
             dt = time.time() - t0
+            if int8_on:  # integer layers of one forward pass
+                res["int8_layers"] = int8.layers_run() // int(math.ceil(F.num_examples / float(F.batch_size)))
+                print("%s: int8_layers = %d" % (datetime.now(), res["int8_layers"]), flush=True)
             if top5:
                 print("%s: precision @ 1 = %.4f recall @ 5 = %.4f [%d examples] (%.1f examples/sec)"
                       % (datetime.now(), p1, r5, F.num_examples, F.num_examples / max(dt, 1e-9)), flush=True)

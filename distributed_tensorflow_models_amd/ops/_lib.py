@@ -207,6 +207,14 @@ _SIGS = {
     "dtm_fq_apply": (_I, [_P, _P, _I, _L, _P, _P]),
     "dtm_fq_apply_bwd": (_I, [_P, _P, _P, _I, _L, _P, _P]),
     "dtm_fq_advance": (_I, [_P, _P]),
+    "dtm_q8_max_reduce": (_I, []),
+    "dtm_q8_weight_rows": (_I, [_I]),
+    "dtm_q8_weight_row_bytes": (_I, [_I, _I, _I]),
+    "dtm_q8_quantize": (_I, [_P, _I, _P, _L, _P, _P]),
+    "dtm_q8_dequantize": (_I, [_P, _P, _I, _L, _P, _P]),
+    "dtm_q8_prepare_weights": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "dtm_q8_conv": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P]),
+    "dtm_q8_depthwise": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P]),
 }
 
 

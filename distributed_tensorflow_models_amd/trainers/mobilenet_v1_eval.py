@@ -8,6 +8,8 @@ flags.DEFINE_float("depth_multiplier", 1.0, "Depth multiplier for mobilenet")
 flags.DEFINE_string("dataset_dir", "", "Location of dataset (alias of --data_dir)")
 flags.DEFINE_boolean("quantize", False, "Quantize training (evaluate the fake-quantised graph)")
 flags.DEFINE_boolean("quant_fused", False, "evaluate through the fused fake-quantisation kernels (stored ranges)")
+flags.DEFINE_boolean("quant_int8", False, "evaluate in 8-bit integer arithmetic where a layer allows it (implies "
+                     "--quant_fused; needs --quantize); the result gains int8_layers")
 
 
 def main(_argv=None):

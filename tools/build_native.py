@@ -22,6 +22,9 @@ OBJ_DIR = os.path.join(ROOT, "build", "obj")
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 CXX = os.environ.get("CXX", "g++")
+# kernel files built without the packed fp32 VALU instructions (v_pk_add / mul / fma_f32)
+NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+NO_PACKED_FP32_SRCS = {"int8.hip"}
 
 
 def _newer(src_list, target):
@@ -55,8 +58,9 @@ def build(force=False, jobs=None, asan=False, verbose=False):
         o = os.path.join(OBJ_DIR, os.path.basename(s) + ".o")
         hip_objs.append(o)
         if force or _newer([s] + kheaders, o):
+            extra = NO_PACKED_FP32 if os.path.basename(s) in NO_PACKED_FP32_SRCS else []
             jobs_list.append([HIPCC, "--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC",
-                              "-munsafe-fp-atomics", "-c", s, "-o", o])
+                              "-munsafe-fp-atomics"] + extra + ["-c", s, "-o", o])
     cpu_objs = []
     for s in cpp_srcs:
         o = os.path.join(OBJ_DIR, os.path.basename(s) + ".o")

@@ -1,6 +1,9 @@
 // Depthwise 2-D convolution (NHWC, TF weight layout [R][S][C][M]) - SURVEY.md K16
 // (slim.separable_conv2d / depthwise_conv2d in MobileNet v1/v2, NASNet, Inception-v2).
-// Bandwidth-bound op: 8 channels per lane (16-B loads) for depth_multiplier 1; scalar lanes for M > 1.
+// The first ("legacy") family: dw_*8, 8 channels per lane (16-B loads), only where M == 1 and 256 % (C/8) == 0 (fast8);
+// every other shape - any other C, M > 1 - runs the scalar *_generic kernels.  dw_*8 re-read their operands once per
+// tap through the caches (dw_wgrad8: x and dy R*S times, a block reduction per tap).  The LDS-tiled one-read family
+// for any C % 8 == 0 at M == 1 is depthwise_tile.hip; ops/depthwise.py chooses between the two.
 //   fwd:   y[n,p,q,c*M+m] = sum_{r,s} x[n, p*st-ph+r*d, q*st-pw+s*d, c] * w[r,s,c,m]
 //   dgrad: gather over the taps that touched (h, w)
 //   wgrad: per-block partial sums over pixels for all R*S taps, then the two-stage row reduction.

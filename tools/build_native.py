@@ -24,7 +24,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 CXX = os.environ.get("CXX", "g++")
 # kernel files built without the packed fp32 VALU instructions (v_pk_add / mul / fma_f32)
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-NO_PACKED_FP32_SRCS = {"int8.hip"}
+NO_PACKED_FP32_SRCS = {"int8.hip", "depthwise_tile.hip"}
 
 
 def _newer(src_list, target):

@@ -518,6 +518,35 @@ def instance_norm(inputs, center=True, scale=True, epsilon=1e-6, activation_fn=N
     return y if fuse_relu else _act(y, activation_fn)
 
 
+@add_arg_scope
+def group_norm(inputs, groups=32, center=True, scale=True, epsilon=1e-6, activation_fn=None, param_initializers=None,
+               reuse=None, variables_collections=None, outputs_collections=None, trainable=True, scope=None,
+               _default_scope="GroupNorm"):
+    """tf.contrib.layers.group_norm on NHWC: per-sample statistics over H, W and each group of C / groups channels."""
+    x = as_tensor(inputs)
+    C = x.shape[-1]
+    if groups < 1 or C % groups != 0:
+        raise ValueError("group_norm: %d channels do not divide into %d groups" % (C, groups))
+    pi = param_initializers or {}
+    with variable_scope(scope, _default_scope, reuse=reuse):
+        beta = variable("beta", (C,), initializer=pi.get("beta", ("constant", 0.0)), trainable=trainable) \
+            if center else None
+        gamma = variable("gamma", (C,), initializer=pi.get("gamma", ("constant", 1.0)), trainable=trainable) \
+            if scale else None
+    from ..ops.groupnorm import group_norm as _gnorm
+    fuse_relu = activation_fn in (torch.relu, E.relu, "relu")
+    y = _gnorm(x, groups, gamma, beta, epsilon, relu=fuse_relu)  # HIP kernels on CUDA (groupnorm.hip)
+    return y if fuse_relu else _act(y, activation_fn)
+
+
+@add_arg_scope
+def layer_norm(inputs, center=True, scale=True, activation_fn=None, reuse=None, variables_collections=None,
+               outputs_collections=None, trainable=True, scope=None):
+    """tf.contrib.layers.layer_norm on NHWC: one group over H, W and all channels; TF's variance epsilon 1e-12."""
+    return group_norm(inputs, groups=1, center=center, scale=scale, epsilon=1e-12, activation_fn=activation_fn,
+                      reuse=reuse, trainable=trainable, scope=scope, _default_scope="LayerNorm")
+
+
 def leaky_relu(x, alpha=0.2):
     from ..ops.activation import leaky_relu as _lrelu
     return _lrelu(as_tensor(x), alpha)

@@ -56,6 +56,8 @@ def define_eval_flags(flags, preset):
             ("batch_size", flags.DEFINE_integer, p["batch_size"], "Number of images to process in a batch."),
             ("data_dir", flags.DEFINE_string, p["data_dir"], "Path to the data directory."),
             ("resnet_size", flags.DEFINE_integer, 32, "The size of the ResNet model to use."),
+            ("norm", flags.DEFINE_string, "batch", "batch | group: as the checkpoint was trained"),
+            ("norm_groups", flags.DEFINE_integer, 32, "groups of --norm group"),
             ("use_ema", flags.DEFINE_boolean, d[4], "restore ExponentialMovingAverage shadows"),
             ("synthetic_data", flags.DEFINE_boolean, False, "evaluate on synthetic batches"),
             ("max_evals", flags.DEFINE_integer, 0, "stop after N evaluations (0 = forever)"),
@@ -187,6 +189,7 @@ def evaluate(preset, flags):
     top5 = EVAL_DEFAULTS[preset][5]
     device = torch.device("cuda", 0) if torch.cuda.is_available() else torch.device("cpu")
     kw = {"resnet_size": F.resnet_size} if cfg["model"] == "cifar10_resnet_v2" else {}
+    kw.update(trainer.norm_model_kw(cfg["model"], F.norm, F.norm_groups))
     if cfg["model"].startswith("mobilenet") and "depth_multiplier" in F and F.depth_multiplier != 1.0:
         kw["depth_multiplier"] = F.depth_multiplier
     if "quantize" in F and F.quantize:  # create_eval_graph (mobilenet_v1_eval.py:126-127)

@@ -153,6 +153,23 @@ class BatchNorm(Layer):
                             self.decay, self.eps, relu, residual, self.bessel)
 
 
+class GroupNorm(Layer):
+    """Group normalisation: variables <scope>/{beta,gamma}, no buffers (the statistics are per sample, in training
+    and in evaluation alike).  Call shape of BatchNorm without the residual."""
+
+    def __init__(self, scope, channels, groups, epsilon=1e-5, center=True, scale=True):
+        super().__init__(scope)
+        if groups < 1 or channels % groups != 0:
+            raise ValueError("GroupNorm %s: %d channels do not divide into %d groups" % (scope, channels, groups))
+        self.C, self.groups, self.eps = channels, groups, epsilon
+        self.beta = make_param((channels,), _join(scope, "beta"), ("constant", 0.0)) if center else None
+        self.gamma = make_param((channels,), _join(scope, "gamma"), ("constant", 1.0)) if scale else None
+
+    def forward(self, x, training=True, relu=False):
+        from ..ops.groupnorm import group_norm
+        return group_norm(as_tensor(x), self.groups, self.gamma, self.beta, self.eps, relu)
+
+
 class Conv2d(Layer):
     """slim.conv2d (and old-slim ops.conv2d): conv -> [BatchNorm | +bias] -> activation.
 

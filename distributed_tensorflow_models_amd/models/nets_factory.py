@@ -78,6 +78,11 @@ networks_map = {
 }
 
 
+def accepts_norm(name):
+    """The pre-activation ResNets take norm='batch' | 'group' and norm_groups."""
+    return name in ("cifar10_resnet_v2", "imagenet_resnet_v2") or name.startswith("resnet_v2_")
+
+
 def build(name, num_classes=1000, **kw):
     if name not in networks_map:
         raise ValueError("Name of network unknown %s" % name)

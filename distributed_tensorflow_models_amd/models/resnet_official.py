@@ -12,7 +12,7 @@ root/dense/{kernel,bias}  (SURVEY.md §5.4).
 import torch
 
 from ..ops import nn as F
-from .layers import BatchNorm, Conv2d, FullyConnected, Layer
+from .layers import BatchNorm, Conv2d, FullyConnected, GroupNorm, Layer
 
 _BN = dict(decay=0.997, epsilon=1e-5, scale=True, bessel=True)
 
@@ -49,21 +49,31 @@ class _BNLayer(BatchNorm):
         super().__init__(name, c, **_BN)
 
 
+def _norm_factory(nm, norm, groups):
+    """(channels) -> the next norm layer in creation order: tf.layers names batch_normalization{,_1..}, or
+    group_normalization{,_1..} with ``norm='group'`` (beta and gamma only, eps 1e-5)."""
+    if norm == "batch":
+        return lambda c: _BNLayer(nm("batch_normalization"), c)
+    if norm == "group":
+        return lambda c: GroupNorm(nm("group_normalization"), c, groups, epsilon=_BN["epsilon"])
+    raise ValueError("norm must be 'batch' or 'group', got %r" % (norm,))
+
+
 class _Block(Layer):
-    def __init__(self, nm, cin, filters, stride, bottleneck, projection, wd):
+    def __init__(self, nm, cin, filters, stride, bottleneck, projection, wd, mk_norm):
         super().__init__("")
         out = filters * 4 if bottleneck else filters
-        self.bn1 = _BNLayer(nm("batch_normalization"), cin)
+        self.bn1 = mk_norm(cin)
         self.proj = _Conv(nm("conv2d"), cin, out, 1, stride, wd) if projection else None
         if bottleneck:
             self.c1 = _Conv(nm("conv2d"), cin, filters, 1, 1, wd)
-            self.bn2 = _BNLayer(nm("batch_normalization"), filters)
+            self.bn2 = mk_norm(filters)
             self.c2 = _Conv(nm("conv2d"), filters, filters, 3, stride, wd)
-            self.bn3 = _BNLayer(nm("batch_normalization"), filters)
+            self.bn3 = mk_norm(filters)
             self.c3 = _Conv(nm("conv2d"), filters, out, 1, 1, wd)
         else:
             self.c1 = _Conv(nm("conv2d"), cin, filters, 3, stride, wd)
-            self.bn2 = _BNLayer(nm("batch_normalization"), filters)
+            self.bn2 = mk_norm(filters)
             self.c2 = _Conv(nm("conv2d"), filters, filters, 3, 1, wd)
         self.bottleneck = bottleneck
 
@@ -84,21 +94,22 @@ class CifarResNetV2(Layer):
     """cifar10_resnet_v2_generator(resnet_size, num_classes): resnet_size = 6n + 2."""
     default_image_size = 32
 
-    def __init__(self, resnet_size=32, num_classes=10, scope="root", weight_decay=0.0):
+    def __init__(self, resnet_size=32, num_classes=10, scope="root", weight_decay=0.0, norm="batch", norm_groups=32):
         super().__init__(scope)
         if resnet_size % 6 != 2:
             raise ValueError("resnet_size must be 6n + 2:", resnet_size)
         n = (resnet_size - 2) // 6
         nm = _Namer(scope)
+        mk_norm = _norm_factory(nm, norm, norm_groups)
         self.initial = _Conv(nm("conv2d"), 3, 16, 3, 1, weight_decay)
         blocks, cin = [], 16
         for filters, stride in ((16, 1), (32, 2), (64, 2)):
             for i in range(n):
                 blocks.append(_Block(nm, cin, filters, stride if i == 0 else 1, False, i == 0,
-                                    weight_decay))
+                                    weight_decay, mk_norm))
                 cin = filters
         self.blocks = torch.nn.ModuleList(blocks)
-        self.final_bn = _BNLayer(nm("batch_normalization"), 64)
+        self.final_bn = mk_norm(64)
         self.dense = FullyConnected(nm("dense"), 64, num_classes, None, None, True, weight_decay, "xavier")
         _rename(self.dense, {"weights": self.dense.scope + "/kernel", "biases": self.dense.scope + "/bias"})
 
@@ -120,21 +131,22 @@ class ImagenetResNetV2(Layer):
     """imagenet_resnet_v2(resnet_size, num_classes) (resnet/resnet_model.py:285-370)."""
     default_image_size = 224
 
-    def __init__(self, resnet_size=50, num_classes=1001, scope="", weight_decay=0.0):
+    def __init__(self, resnet_size=50, num_classes=1001, scope="", weight_decay=0.0, norm="batch", norm_groups=32):
         super().__init__(scope)
         kind, layers = IMAGENET_CFG[resnet_size]
         bott = kind == "bottleneck"
         nm = _Namer(scope)
+        mk_norm = _norm_factory(nm, norm, norm_groups)
         self.initial = _Conv(nm("conv2d"), 3, 64, 7, 2, weight_decay)
         blocks, cin = [], 64
         for li, (filters, stride) in enumerate(((64, 1), (128, 2), (256, 2), (512, 2))):
             out = filters * 4 if bott else filters
             for i in range(layers[li]):
                 blocks.append(_Block(nm, cin, filters, stride if i == 0 else 1, bott, i == 0,
-                                     weight_decay))
+                                     weight_decay, mk_norm))
                 cin = out
         self.blocks = torch.nn.ModuleList(blocks)
-        self.final_bn = _BNLayer(nm("batch_normalization"), cin)
+        self.final_bn = mk_norm(cin)
         self.dense = FullyConnected(nm("dense"), cin, num_classes, None, None, True, weight_decay, "xavier")
         _rename(self.dense, {"weights": self.dense.scope + "/kernel", "biases": self.dense.scope + "/bias"})
 

@@ -51,11 +51,11 @@ def _conv2d_same(x, num_outputs, k, stride, scope, rate=1):
     return slim.conv2d(x, num_outputs, k, stride=stride, rate=rate, padding=(pad, pad), scope=scope)
 
 
-def _bottleneck_v2(x, depth, depth_bottleneck, stride, scope, rate=1, ep=None):
+def _bottleneck_v2(x, depth, depth_bottleneck, stride, scope, rate=1, ep=None, norm_fn=slim.batch_norm):
     with slim.variable_scope(scope):
         with slim.variable_scope("bottleneck_v2") as vs:
             depth_in = as_tensor(x).shape[-1]
-            preact = slim.batch_norm(x, activation_fn=relu, scope="preact")
+            preact = norm_fn(x, activation_fn=relu, scope="preact")
             if depth == depth_in:
                 shortcut = _subsample(x, stride)
             else:
@@ -84,14 +84,21 @@ def resnet_v2_block(scope, base_depth, num_units, stride):
 
 def resnet_v2(images, num_classes=1000, is_training=True, depth=50, weight_decay=0.0001, scope=None,
               global_pool=True, spatial_squeeze=True, blocks=None, output_stride=None, include_root_block=True,
-              store_non_strided_activations=False):
+              store_non_strided_activations=False, norm="batch", norm_groups=32):
     """slim resnet_v2 generator (reference vgg/nets/resnet_v2.py:111-224): pre-activation
     bottlenecks, root conv without BN, ``postnorm`` BN-ReLU, atrous ``output_stride``.  Endpoints:
-    every conv output, unit, block, global_pool, logits, spatial_squeeze, predictions."""
+    every conv output, unit, block, global_pool, logits, spatial_squeeze, predictions.
+    ``norm='group'``: every batch_norm (the convs' normalizer, ``preact``, ``postnorm``; the scopes keep their
+    names) becomes slim.group_norm with ``norm_groups`` groups: beta and gamma only, no moving statistics."""
     from .resnet_v1 import stack_blocks_plan
     scope = scope or "resnet_v2_%d" % depth
     ep = {}
     bn = dict(decay=0.997, epsilon=1e-5, scale=True)
+    norm_fn = slim.batch_norm
+    if norm == "group":
+        norm_fn, bn = slim.group_norm, dict(groups=norm_groups, epsilon=1e-5)
+    elif norm != "batch":
+        raise ValueError("norm must be 'batch' or 'group', got %r" % (norm,))
     if blocks is None:
         blocks = [(base, n, 2 if bi < 3 else 1) for bi, (base, n) in
                   enumerate(zip([64, 128, 256, 512], RESNET_V2_BLOCKS[depth]))]
@@ -102,8 +109,8 @@ def resnet_v2(images, num_classes=1000, is_training=True, depth=50, weight_decay
     plan = stack_blocks_plan(blocks, output_stride, store_non_strided_activations)
     with slim.arg_scope([slim.conv2d], weights_regularizer=slim.l2_regularizer(weight_decay),
                         weights_initializer=slim.variance_scaling_initializer(), activation_fn=relu,
-                        normalizer_fn=slim.batch_norm, normalizer_params=bn):
-        with slim.arg_scope([slim.batch_norm], **bn), slim.arg_scope([slim.max_pool2d], padding="SAME"):
+                        normalizer_fn=norm_fn, normalizer_params=bn):
+        with slim.arg_scope([norm_fn], **bn), slim.arg_scope([slim.max_pool2d], padding="SAME"):
             with slim.variable_scope(scope) as vs:
                 net = images
                 if include_root_block:
@@ -114,10 +121,10 @@ def resnet_v2(images, num_classes=1000, is_training=True, depth=50, weight_decay
                 for bi, ((base, n, _), (uplan, sub)) in enumerate(zip(blocks, plan)):
                     with slim.variable_scope("block%d" % (bi + 1)):
                         for u, (stride, rate) in enumerate(uplan):
-                            net = _bottleneck_v2(net, base * 4, base, stride, "unit_%d" % (u + 1), rate, ep)
+                            net = _bottleneck_v2(net, base * 4, base, stride, "unit_%d" % (u + 1), rate, ep, norm_fn)
                     ep["%s/block%d" % (vs, bi + 1)] = net
                     net = _subsample(net, sub)
-                net = slim.batch_norm(net, activation_fn=relu, scope="postnorm")
+                net = norm_fn(net, activation_fn=relu, scope="postnorm")
                 if global_pool:
                     net = F.global_avg_pool(net).reshape(net.shape[0], 1, 1, -1)
                     ep["global_pool"] = net

@@ -224,6 +224,19 @@ def compress_config(FLAGS, mode):
     return GradCompress(ratio, FLAGS.grad_compress_begin_step)  # (its own checks: a ratio in (0, 1], a step >= 0)
 
 
+def norm_model_kw(model, norm, groups):
+    """--norm / --norm_groups as model keywords: both, when ``model`` takes them (nets_factory.accepts_norm), else
+    none; group norm asked of any other model is an error."""
+    if norm not in ("batch", "group"):
+        raise ValueError("--norm must be batch or group, got %r" % (norm,))
+    if nets_factory.accepts_norm(model):
+        return dict(norm=norm, norm_groups=int(groups))
+    if norm == "group":
+        raise ValueError("--norm group: the model %r normalises with BatchNorm only (group norm is built into "
+                         "cifar10_resnet_v2, imagenet_resnet_v2 and resnet_v2_*)" % model)
+    return {}
+
+
 def parse_model_kw(text):
     """"k=v,..." -> {k: int or float}: the numeric model keywords of --distill_teacher_kw."""
     out = {}
@@ -267,6 +280,10 @@ def define_common_flags(flags, preset):
             ("max_steps", I, p["max_steps"], "Number of batches to run."),
             ("log_device_placement", B, preset == "cnn", "Whether to log device placement."),
             ("resnet_size", I, 32, "The size of the ResNet model to use."),
+            ("norm", S, "batch", "batch | group: the normalisation of the pre-activation ResNets (group: per-sample "
+             "statistics, no moving averages; independent of the batch size and of --accum_steps)"),
+            ("norm_groups", I, 32, "groups of --norm group; every width must divide (the CIFAR ResNet's 16 / 32 / 64 "
+             "want 8)"),
             ("protocol", S, "grpc", "accepted for compatibility; transport is RCCL/gloo"),
             ("save_interval_secs", I, p["save_secs"], "Save interval seconds."),
             ("save_every_steps", I, 0, "also checkpoint every N global steps (0 = time-based only)"),
@@ -455,6 +472,7 @@ def train(preset, flags, default_mode="bsp"):
         raise ValueError(LAMB_BSP_ONLY % mode)
     if optimizer == "lamb" and FLAGS.clip_global_norm > 0:
         raise ValueError(LAMB_NO_CLIP)
+    norm_kw = norm_model_kw(cfg["model"], FLAGS.norm, FLAGS.norm_groups)
     accum = int(FLAGS.accum_steps)
     if accum < 1:
         raise ValueError("--accum_steps must be at least 1, got %d" % accum)
@@ -506,6 +524,7 @@ def train(preset, flags, default_mode="bsp"):
 
     # ---- model ---------------------------------------------------------------------------------
     mkw = dict(cfg.get("model_kw", {}))
+    mkw.update(norm_kw)
     if cfg["model"] == "cifar10_resnet_v2":
         mkw["resnet_size"] = FLAGS.resnet_size
     if cfg["model"].startswith("mobilenet") and FLAGS.depth_multiplier != 1.0:

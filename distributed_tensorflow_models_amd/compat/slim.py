@@ -623,6 +623,36 @@ convolution2d_transpose = conv2d_transpose
 
 
 @add_arg_scope
+def grouped_conv2d(inputs, num_outputs, kernel_size, groups, stride=1, padding="SAME", activation_fn=torch.relu,
+                   normalizer_fn=None, normalizer_params=None, weights_initializer="xavier",
+                   weights_regularizer=None, biases_initializer=("constant", 0.0), trainable=True, scope=None,
+                   reuse=None):
+    """Grouped convolution of equal input and output width (ResNeXt): TF filter [kh, kw, in / groups, num_outputs]
+    (stored [num_outputs, kh, kw, in / groups]); HIP kernels on CUDA (groupconv.hip).  The normalizer runs on the
+    output tensor; grouped layers are not fake-quantised."""
+    from ..ops.groupconv import grouped_conv2d as _gconv
+    if _store.quant is not None:
+        raise ValueError("grouped_conv2d: grouped layers are not quantised; build the model without --quantize")
+    x = as_tensor(inputs)
+    kh, kw = _pair(kernel_size)
+    cin = x.shape[-1]
+    if groups < 1 or cin % groups:
+        raise ValueError("grouped_conv2d: %d input channels do not divide into %d groups" % (cin, groups))
+    with variable_scope(scope, "GroupedConv", reuse=reuse):
+        w = variable("weights", (num_outputs, kh, kw, cin // groups), initializer=weights_initializer,
+                     regularizer=weights_regularizer, trainable=trainable, tf_layout="KRSC->HWIO")
+        b = None
+        if normalizer_fn is None and biases_initializer is not None:
+            b = variable("biases", (num_outputs,), initializer=biases_initializer, trainable=trainable)
+        y = _gconv(x, w, groups, stride, padding)
+        if normalizer_fn is not None:
+            return normalizer_fn(y, activation_fn=activation_fn, **(normalizer_params or {}))
+        if b is not None:
+            y = y + b.to(y.dtype)
+        return _act(y, activation_fn)
+
+
+@add_arg_scope
 def separable_conv2d(inputs, num_outputs, kernel_size, depth_multiplier=1, stride=1, padding="SAME", rate=1,
                      activation_fn=torch.relu, normalizer_fn=None, normalizer_params=None,
                      weights_initializer="xavier", weights_regularizer=None, biases_initializer=("constant", 0.0),

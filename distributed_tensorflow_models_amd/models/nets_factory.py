@@ -52,6 +52,9 @@ networks_map = {
     "resnet_v2_101": _slim(slim_nets.resnet_v2, 224, depth=101),
     "resnet_v2_152": _slim(slim_nets.resnet_v2, 224, depth=152),
     "resnet_v2_200": _slim(slim_nets.resnet_v2, 224, depth=200),
+    "resnext_50_32x4d": _slim(slim_nets.resnext, 224, depth=50, cardinality=32, base_width=4),
+    "resnext_101_32x4d": _slim(slim_nets.resnext, 224, depth=101, cardinality=32, base_width=4),
+    "resnext_101_64x4d": _slim(slim_nets.resnext, 224, depth=101, cardinality=64, base_width=4),
     "cifar10_resnet_v2": lambda num_classes=10, resnet_size=32, **kw: resnet_official.CifarResNetV2(
         resnet_size, num_classes, **kw),
     "imagenet_resnet_v2": lambda num_classes=1001, resnet_size=50, **kw: resnet_official.ImagenetResNetV2(

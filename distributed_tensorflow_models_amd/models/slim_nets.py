@@ -3,7 +3,7 @@ registry of the reference (vgg/nets/nets_factory.py:39-100).  Structures, endpoi
 variable names follow the slim definitions (reference vgg/nets/*.py); each model is verified
 against the reference tests' golden numbers (tests/test_models.py).
 
-Contents: resnet_v2_{50,101,152,200} (slim pre-activation), inception_v1, inception_v2,
+Contents: resnet_v2_{50,101,152,200} (slim pre-activation), resnext, inception_v1, inception_v2,
 inception_v3 (new slim; ``cifar_variant`` = the reference's VALID->SAME patch), inception_v4,
 inception_resnet_v2, mobilenet_v1 (+0.75/0.5/0.25), mobilenet_v2.
 """
@@ -125,6 +125,65 @@ def resnet_v2(images, num_classes=1000, is_training=True, depth=50, weight_decay
                     ep["%s/block%d" % (vs, bi + 1)] = net
                     net = _subsample(net, sub)
                 net = norm_fn(net, activation_fn=relu, scope="postnorm")
+                if global_pool:
+                    net = F.global_avg_pool(net).reshape(net.shape[0], 1, 1, -1)
+                    ep["global_pool"] = net
+                if num_classes:
+                    net = slim.conv2d(net, num_classes, 1, activation_fn=None, normalizer_fn=None, scope="logits")
+                    ep[vs + "/logits"] = net
+                    if spatial_squeeze:
+                        net = _squeeze(net)
+                        ep[vs + "/spatial_squeeze"] = net
+                    ep["predictions"] = torch.softmax(as_tensor(net).float(), -1)
+    return net, ep
+
+
+# =============================================================================================
+# ResNeXt (Xie et al. 2017, "Aggregated Residual Transformations for Deep Neural Networks"): post-activation
+# bottlenecks whose 3x3 is a grouped conv of `cardinality` groups
+def _bottleneck_next(x, depth, width, groups, stride, scope, ep):
+    with slim.variable_scope(scope):
+        with slim.variable_scope("bottleneck") as vs:
+            if as_tensor(x).shape[-1] == depth and stride == 1:
+                shortcut = x
+            else:
+                shortcut = ep[vs + "/shortcut"] = slim.conv2d(x, depth, 1, stride=stride, activation_fn=None,
+                                                              scope="shortcut")
+            r = slim.conv2d(x, width, 1, stride=1, scope="conv1")
+            r2 = slim.grouped_conv2d(r, width, 3, groups, stride=stride, padding="SAME", scope="conv2")
+            r3 = slim.conv2d(r2, depth, 1, stride=1, activation_fn=None, scope="conv3")
+            out = relu(as_tensor(shortcut) + as_tensor(r3))
+            for name, v in (("conv1", r), ("conv2", r2), ("conv3", r3)):
+                ep[vs + "/" + name] = v
+            ep[vs] = out
+            return out
+
+
+def resnext(images, num_classes=1000, is_training=True, depth=50, cardinality=32, base_width=4, weight_decay=1e-4,
+            blocks=None, scope=None, global_pool=True, spatial_squeeze=True):
+    """ResNeXt-<depth> (<cardinality>x<base_width>d) in the paper's and torchvision's convention: stage i has
+    bottleneck width cardinality * base_width * 2^i (D = base_width * 2^i channels per group) and output depth
+    256 * 2^i; stride 2 on the grouped 3x3 of the first unit of stages 2 - 4; 1x1 projection shortcut with BN where
+    depth or stride changes.  ``blocks``: units per stage.  Stem and head as resnet_v2 (with BN + ReLU on the stem)."""
+    scope = scope or "resnext_%d_%dx%dd" % (depth, cardinality, base_width)
+    ep = {}
+    bn = dict(decay=0.997, epsilon=1e-5, scale=True)
+    if blocks is None:
+        blocks = RESNET_V2_BLOCKS[depth]
+    convs = [slim.conv2d, slim.grouped_conv2d]
+    with slim.arg_scope(convs, weights_regularizer=slim.l2_regularizer(weight_decay),
+                        weights_initializer=slim.variance_scaling_initializer(), activation_fn=relu,
+                        normalizer_fn=slim.batch_norm, normalizer_params=bn):
+        with slim.arg_scope([slim.batch_norm], **bn), slim.arg_scope([slim.max_pool2d], padding="SAME"):
+            with slim.variable_scope(scope) as vs:
+                net = ep[vs + "/conv1"] = _conv2d_same(images, 64, 7, 2, "conv1")
+                net = slim.max_pool2d(net, 3, stride=2, scope="pool1")
+                for bi, n in enumerate(blocks):
+                    with slim.variable_scope("block%d" % (bi + 1)):
+                        for u in range(n):
+                            net = _bottleneck_next(net, 256 << bi, cardinality * base_width << bi, cardinality,
+                                                   2 if bi > 0 and u == 0 else 1, "unit_%d" % (u + 1), ep)
+                    ep["%s/block%d" % (vs, bi + 1)] = net
                 if global_pool:
                     net = F.global_avg_pool(net).reshape(net.shape[0], 1, 1, -1)
                     ep["global_pool"] = net

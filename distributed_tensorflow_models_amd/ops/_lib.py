@@ -162,6 +162,9 @@ _SIGS = {
     "dtm_depthwise_tile_fwd": (_I, [_P, _P, _P, _P, _P]),
     "dtm_depthwise_tile_dgrad": (_I, [_P, _P, _P, _P, _P]),
     "dtm_depthwise_tile_wgrad": (_I, [_P, _P, _P, _P, _P]),
+    "dtm_groupconv_fwd": (_I, [_P, _P, _P, _P, _P]),
+    "dtm_groupconv_dgrad": (_I, [_P, _P, _P, _P, _P]),
+    "dtm_groupconv_wgrad": (_I, [_P, _P, _P, _P, _P]),
     "dtm_set_reduce_policy": (None, [_I, _I, _I]),
     "dtm_bn_apply_ld": (_I, [_P, _P, _P, _P, _L, _I, _I, _I, _P]),
     "dtm_bn_apply_bwd_ld": (_I, [_P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _P]),

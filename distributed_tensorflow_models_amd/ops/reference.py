@@ -47,6 +47,22 @@ def depthwise_conv2d(x, w, stride=1, padding="SAME", dilation=1):
     return _nhwc(y[:, :, :g.P, :g.Q])
 
 
+def grouped_conv2d(x, w, groups, stride=1, padding="SAME"):
+    """x [N,H,W,C], w [K,R,S,C/groups] (KRSC per group; group g owns outputs [g K/groups, (g+1) K/groups) and inputs
+    [g C/groups, (g+1) C/groups)) -> [N,P,Q,K]."""
+    K, R, S, D = w.shape
+    C = x.shape[-1]
+    if C != D * groups or K % groups:
+        raise ValueError("grouped conv: %d inputs, %d outputs and filters of %d channels do not make %d groups"
+                         % (C, K, D, groups))
+    g = conv_geom(tuple(x.shape), (K, R, S, C), stride, padding)
+    xp = _nchw(x)
+    if g.pad_h or g.pad_b or g.pad_w or g.pad_r:
+        xp = F.pad(xp, (g.pad_w, g.pad_r, g.pad_h, g.pad_b))
+    y = F.conv2d(xp, w.permute(0, 3, 1, 2), None, g.stride, 0, 1, groups)
+    return _nhwc(y[:, :, :g.P, :g.Q])
+
+
 def conv2d_transpose(x, w, stride=2, padding="SAME", out_hw=None):
     """TF conv2d_transpose: x [N,H,W,Cin], w [R,S,Cout,Cin] -> [N,H*s,W*s,Cout] (SAME)."""
     N, H, W, Cin = x.shape

@@ -653,6 +653,36 @@ def grouped_conv2d(inputs, num_outputs, kernel_size, groups, stride=1, padding="
 
 
 @add_arg_scope
+def squeeze_excite(inputs, ratio=16, residual=None, activation_fn=None, weights_initializer="xavier",
+                   weights_regularizer=None, trainable=True, scope=None, reuse=None):
+    """Squeeze-and-excitation (Hu et al. 2018): act(inputs * gate + residual), the gate a sigmoid of two FCs on the
+    global average, C -> C // ratio -> C.  The FCs are stored as 1x1 conv filters (TF [1, 1, in, out]) under
+    <scope>/fc1, <scope>/fc2 with zero-initialised biases and no normalizer; HIP kernels on CUDA (se.hip).  SE layers
+    are not fake-quantised."""
+    from ..ops.se import squeeze_excite as _se
+    if _store.quant is not None:
+        raise ValueError("squeeze_excite: SE layers are not quantised; build the model without --quantize")
+    x = as_tensor(inputs)
+    res = None if residual is None else as_tensor(residual)
+    C = x.shape[-1]
+    Cr = C // ratio
+    if Cr < 1:
+        raise ValueError("squeeze_excite: %d channels at ratio %d leave no hidden unit" % (C, ratio))
+    with variable_scope(scope, "SqueezeExcite", reuse=reuse):
+        params = []
+        for name, (out, cin) in (("fc1", (Cr, C)), ("fc2", (C, Cr))):
+            with variable_scope(name):
+                params.append(variable("weights", (out, 1, 1, cin), initializer=weights_initializer,
+                                       regularizer=weights_regularizer, trainable=trainable, tf_layout="KRSC->HWIO"))
+                params.append(variable("biases", (out,), initializer=("constant", 0.0), trainable=trainable))
+    fuse_relu = activation_fn in (torch.relu, E.relu, "relu")
+    if res is not None and res.dtype != x.dtype:
+        res = res.to(x.dtype)
+    y = _se(x, *params, residual=res, relu=fuse_relu)
+    return y if fuse_relu else _act(y, activation_fn)
+
+
+@add_arg_scope
 def separable_conv2d(inputs, num_outputs, kernel_size, depth_multiplier=1, stride=1, padding="SAME", rate=1,
                      activation_fn=torch.relu, normalizer_fn=None, normalizer_params=None,
                      weights_initializer="xavier", weights_regularizer=None, biases_initializer=("constant", 0.0),

@@ -55,6 +55,13 @@ networks_map = {
     "resnext_50_32x4d": _slim(slim_nets.resnext, 224, depth=50, cardinality=32, base_width=4),
     "resnext_101_32x4d": _slim(slim_nets.resnext, 224, depth=101, cardinality=32, base_width=4),
     "resnext_101_64x4d": _slim(slim_nets.resnext, 224, depth=101, cardinality=64, base_width=4),
+    "se_resnext_50_32x4d": _slim(slim_nets.resnext, 224, depth=50, cardinality=32, base_width=4, se_ratio=16,
+                                 scope="se_resnext_50_32x4d"),
+    "se_resnext_101_32x4d": _slim(slim_nets.resnext, 224, depth=101, cardinality=32, base_width=4, se_ratio=16,
+                                  scope="se_resnext_101_32x4d"),
+    # cardinality 1 at base width 64: the 3x3 is the dense conv, the net SE-ResNet-50
+    "se_resnet_50": _slim(slim_nets.resnext, 224, depth=50, cardinality=1, base_width=64, se_ratio=16,
+                          scope="se_resnet_50"),
     "cifar10_resnet_v2": lambda num_classes=10, resnet_size=32, **kw: resnet_official.CifarResNetV2(
         resnet_size, num_classes, **kw),
     "imagenet_resnet_v2": lambda num_classes=1001, resnet_size=50, **kw: resnet_official.ImagenetResNetV2(

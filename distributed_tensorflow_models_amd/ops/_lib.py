@@ -48,6 +48,9 @@ _SIGS = {
     "dtm_groupnorm_ws_floats": (_L, [_I, _I, _I, _I, _I, _I]),
     "dtm_groupnorm_fwd": (_I, [_P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _F, _I, _I, _P]),
     "dtm_groupnorm_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "dtm_se_ws_floats": (_L, [_I, _I, _I, _I, _I, _I]),
+    "dtm_se_fwd": (_I, [_P] * 11 + [_L, _I, _I, _I, _I, _I, _I, _P]),
+    "dtm_se_bwd": (_I, [_P] * 15 + [_L, _I, _I, _I, _I, _I, _I, _P]),
     "dtm_reflect_pad": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "dtm_reflect_pad_bwd": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "dtm_conv_dgrad": (_I, [_P, _P, _P, ctypes.POINTER(ConvDesc), _P]),

@@ -683,6 +683,35 @@ def squeeze_excite(inputs, ratio=16, residual=None, activation_fn=None, weights_
 
 
 @add_arg_scope
+def multi_head_self_attention(inputs, heads=4, trainable=True, scope=None, reuse=None):
+    """Multi-head self-attention over the pixels of NHWC ``inputs`` (BoTNet, Srinivas et al. 2021) with absolute,
+    factorised position keys: one bias-free 1x1 conv <scope>/qkv to [q | k | v] (each head-major; initializer and
+    regularizer from conv2d's arg scope), fp32 position variables <scope>/pos_h [H, C] and <scope>/pos_w [W, C] added
+    to the keys, so that q (k + p)^T is the content plus the position logits, then ops.attention.mhsa (HIP kernels on
+    CUDA, attention.hip) with q and v as views of the conv output.  Attention layers are not fake-quantised."""
+    from ..ops.attention import mhsa as _mhsa
+    if _store.quant is not None:
+        raise ValueError("multi_head_self_attention: attention layers are not quantised; build the model without "
+                         "--quantize")
+    x = as_tensor(inputs)
+    _, H, W, C = x.shape
+    if heads < 1 or C % heads != 0:
+        raise ValueError("multi_head_self_attention: %d channels do not divide into %d heads" % (C, heads))
+    with variable_scope(scope, "MHSA", reuse=reuse):
+        qkv = as_tensor(conv2d(x, 3 * C, 1, normalizer_fn=None, activation_fn=None, biases_initializer=None,
+                               trainable=trainable, scope="qkv"))
+        init = ("normal", (C // heads) ** -0.5)
+        pos_h = variable("pos_h", (H, C), initializer=init, trainable=trainable)
+        pos_w = variable("pos_w", (W, C), initializer=init, trainable=trainable)
+    if tuple(pos_h.shape) != (H, C) or tuple(pos_w.shape) != (W, C):
+        raise ValueError("multi_head_self_attention: position variables of a %dx%d map, called on a %dx%d map"
+                         % (pos_h.shape[0], pos_w.shape[0], H, W))
+    q, k, v = qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:]
+    k = (k.float() + pos_h[:, None, :] + pos_w[None, :, :]).to(qkv.dtype)
+    return _mhsa(q, k, v, heads)
+
+
+@add_arg_scope
 def separable_conv2d(inputs, num_outputs, kernel_size, depth_multiplier=1, stride=1, padding="SAME", rate=1,
                      activation_fn=torch.relu, normalizer_fn=None, normalizer_params=None,
                      weights_initializer="xavier", weights_regularizer=None, biases_initializer=("constant", 0.0),

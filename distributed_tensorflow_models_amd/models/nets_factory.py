@@ -62,6 +62,9 @@ networks_map = {
     # cardinality 1 at base width 64: the 3x3 is the dense conv, the net SE-ResNet-50
     "se_resnet_50": _slim(slim_nets.resnext, 224, depth=50, cardinality=1, base_width=64, se_ratio=16,
                           scope="se_resnet_50"),
+    # BoTNet-50: ResNet-50 whose last stage attends over its pixels instead of convolving 3x3 (ops/attention.py)
+    "botnet_50": _slim(slim_nets.resnext, 224, depth=50, cardinality=1, base_width=64, mhsa_heads=4,
+                       scope="botnet_50"),
     "cifar10_resnet_v2": lambda num_classes=10, resnet_size=32, **kw: resnet_official.CifarResNetV2(
         resnet_size, num_classes, **kw),
     "imagenet_resnet_v2": lambda num_classes=1001, resnet_size=50, **kw: resnet_official.ImagenetResNetV2(

@@ -141,7 +141,7 @@ def resnet_v2(images, num_classes=1000, is_training=True, depth=50, weight_decay
 # =============================================================================================
 # ResNeXt (Xie et al. 2017, "Aggregated Residual Transformations for Deep Neural Networks"): post-activation
 # bottlenecks whose 3x3 is a grouped conv of `cardinality` groups
-def _bottleneck_next(x, depth, width, groups, stride, scope, ep, se_ratio=0):
+def _bottleneck_next(x, depth, width, groups, stride, scope, ep, se_ratio=0, mhsa_heads=0):
     with slim.variable_scope(scope):
         with slim.variable_scope("bottleneck") as vs:
             if as_tensor(x).shape[-1] == depth and stride == 1:
@@ -150,7 +150,13 @@ def _bottleneck_next(x, depth, width, groups, stride, scope, ep, se_ratio=0):
                 shortcut = ep[vs + "/shortcut"] = slim.conv2d(x, depth, 1, stride=stride, activation_fn=None,
                                                               scope="shortcut")
             r = slim.conv2d(x, width, 1, stride=1, scope="conv1")
-            r2 = slim.grouped_conv2d(r, width, 3, groups, stride=stride, padding="SAME", scope="conv2")
+            if mhsa_heads > 0:  # BoTNet: attention over the unit's input map, then the stride as an average pool
+                r2 = ep[vs + "/mhsa"] = slim.multi_head_self_attention(r, mhsa_heads, scope="mhsa")
+                if stride == 2:
+                    r2 = slim.avg_pool2d(r2, 2, stride=2)
+                r2 = slim.batch_norm(r2, activation_fn=relu, scope="mhsa/BatchNorm")
+            else:
+                r2 = slim.grouped_conv2d(r, width, 3, groups, stride=stride, padding="SAME", scope="conv2")
             r3 = slim.conv2d(r2, depth, 1, stride=1, activation_fn=None, scope="conv3")
             if se_ratio > 0:  # the gate, the shortcut add and the ReLU in one pass (ops/se.py)
                 out = ep[vs + "/se"] = slim.squeeze_excite(r3, se_ratio, residual=shortcut, activation_fn=relu,
@@ -158,19 +164,22 @@ def _bottleneck_next(x, depth, width, groups, stride, scope, ep, se_ratio=0):
             else:
                 out = relu(as_tensor(shortcut) + as_tensor(r3))
             for name, v in (("conv1", r), ("conv2", r2), ("conv3", r3)):
-                ep[vs + "/" + name] = v
+                if not (mhsa_heads > 0 and name == "conv2"):
+                    ep[vs + "/" + name] = v
             ep[vs] = out
             return out
 
 
 def resnext(images, num_classes=1000, is_training=True, depth=50, cardinality=32, base_width=4, weight_decay=1e-4,
-            blocks=None, scope=None, global_pool=True, spatial_squeeze=True, se_ratio=0):
+            blocks=None, scope=None, global_pool=True, spatial_squeeze=True, se_ratio=0, mhsa_heads=0):
     """ResNeXt-<depth> (<cardinality>x<base_width>d) in the paper's and torchvision's convention: stage i has
     bottleneck width cardinality * base_width * 2^i (D = base_width * 2^i channels per group) and output depth
     256 * 2^i; stride 2 on the grouped 3x3 of the first unit of stages 2 - 4; 1x1 projection shortcut with BN where
     depth or stride changes.  ``blocks``: units per stage.  Stem and head as resnet_v2 (with BN + ReLU on the stem).
     ``se_ratio`` > 0 puts a squeeze-and-excitation gate of C / se_ratio hidden units on every unit's conv3 output
-    (SE-ResNeXt; with cardinality 1 and base_width 64 SE-ResNet)."""
+    (SE-ResNeXt; with cardinality 1 and base_width 64 SE-ResNet).  ``mhsa_heads`` > 0 replaces the 3x3 of every unit of
+    the last stage by multi-head self-attention over the unit's input map (BoTNet, Srinivas et al. 2021: attention,
+    a 2x2 average pool where the unit has stride 2, BN + ReLU); the stage's map size is then fixed by the first call."""
     scope = scope or "resnext_%d_%dx%dd" % (depth, cardinality, base_width)
     ep = {}
     bn = dict(decay=0.997, epsilon=1e-5, scale=True)
@@ -190,7 +199,8 @@ def resnext(images, num_classes=1000, is_training=True, depth=50, cardinality=32
                     with slim.variable_scope("block%d" % (bi + 1)):
                         for u in range(n):
                             net = _bottleneck_next(net, 256 << bi, cardinality * base_width << bi, cardinality,
-                                                   2 if bi > 0 and u == 0 else 1, "unit_%d" % (u + 1), ep, se_ratio)
+                                                   2 if bi > 0 and u == 0 else 1, "unit_%d" % (u + 1), ep, se_ratio,
+                                                   mhsa_heads if bi == len(blocks) - 1 else 0)
                     ep["%s/block%d" % (vs, bi + 1)] = net
                 if global_pool:
                     net = F.global_avg_pool(net).reshape(net.shape[0], 1, 1, -1)

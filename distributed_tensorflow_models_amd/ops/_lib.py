@@ -51,6 +51,8 @@ _SIGS = {
     "dtm_se_ws_floats": (_L, [_I, _I, _I, _I, _I, _I]),
     "dtm_se_fwd": (_I, [_P] * 11 + [_L, _I, _I, _I, _I, _I, _I, _P]),
     "dtm_se_bwd": (_I, [_P] * 15 + [_L, _I, _I, _I, _I, _I, _I, _P]),
+    "dtm_mhsa_fwd": (_I, [_P] * 5 + [_L, _L, _L, _I, _I, _I, _I, _F, _P]),
+    "dtm_mhsa_bwd": (_I, [_P] * 10 + [_L, _L, _L, _I, _I, _I, _I, _F, _P]),
     "dtm_reflect_pad": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "dtm_reflect_pad_bwd": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "dtm_conv_dgrad": (_I, [_P, _P, _P, ctypes.POINTER(ConvDesc), _P]),

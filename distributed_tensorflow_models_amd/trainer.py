@@ -106,6 +106,11 @@ PRESETS = {
                          batch_size=256, lr=0.1, lr_scale_workers=True, decay_epochs=30.0, decay_factor=0.1,
                          optimizer="momentum", momentum=0.9, ema=None, wd_all=None, max_steps=1000, save_secs=600,
                          log_style="standard", max_to_keep=5, train_dir="/tmp/se_resnext50_train", data_dir=""),
+    # BoTNet-50 (self-attention in the last stage, ops/attention.py) with the same recipe
+    "botnet50": dict(model="botnet_50", num_classes=1000, dataset="synthetic_imagenet", image_size=224,
+                     batch_size=256, lr=0.1, lr_scale_workers=True, decay_epochs=30.0, decay_factor=0.1,
+                     optimizer="momentum", momentum=0.9, ema=None, wd_all=None, max_steps=1000, save_secs=600,
+                     log_style="standard", max_to_keep=5, train_dir="/tmp/botnet50_train", data_dir=""),
     # BASELINE config #1 plumbing: LeNet on synthetic MNIST
     "lenet": dict(model="lenet", num_classes=10, dataset="synthetic_mnist", image_size=28, batch_size=64, lr=0.01,
                   lr_scale_workers=True, decay_epochs=100.0, decay_factor=0.1, optimizer="sgd", ema=None,

@@ -7,7 +7,7 @@
 // NHWC, bf16 or fp32 storage, fp32 math.  Elementwise kernels move 8 elements (16 B of bf16) per
 // thread.  Instance norm: one block per (sample, 64-channel group); 8 chunk-lanes x 32 pixel-lanes
 // stride over H*W with shifted sums (x - x[first pixel]) so a large mean does not cancel the variance.
-#include "common.h"
+#include "nhwc8.h"
 
 namespace dtm {
 
@@ -27,45 +27,25 @@ __device__ __forceinline__ float act_d(float x, int kind, float alpha) {
 
 template <bool BF16>
 __device__ __forceinline__ void load8(const void* p, long i, long n, float (&v)[8]) {
-  if (BF16) {
-    const bf16_t* x = (const bf16_t*)p;
-    if (i + 8 <= n) {
-      const uint4 u = *(const uint4*)(x + i);
-      const uint32_t w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) { v[2 * j] = lo_bf(w[j]); v[2 * j + 1] = hi_bf(w[j]); }
-    } else {
-      for (int j = 0; j < 8; ++j) v[j] = i + j < n ? bf2f(x[i + j]) : 0.f;
-    }
+  if (i + 8 <= n) {
+    ld8<BF16>(p, (size_t)i, v);
+  } else if (BF16) {
+    for (int j = 0; j < 8; ++j) v[j] = i + j < n ? bf2f(((const bf16_t*)p)[i + j]) : 0.f;
   } else {
-    const float* x = (const float*)p;
-    if (i + 8 <= n) {
-      const float4 a = *(const float4*)(x + i), b = *(const float4*)(x + i + 4);
-      v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-    } else {
-      for (int j = 0; j < 8; ++j) v[j] = i + j < n ? x[i + j] : 0.f;
-    }
+    for (int j = 0; j < 8; ++j) v[j] = i + j < n ? ((const float*)p)[i + j] : 0.f;
   }
 }
 
 template <bool BF16>
 __device__ __forceinline__ void store8(void* p, long i, long n, const float (&v)[8]) {
-  if (BF16) {
-    bf16_t* y = (bf16_t*)p;
-    if (i + 8 <= n) {
-      *(uint4*)(y + i) = make_uint4(pack2bf(v[0], v[1]), pack2bf(v[2], v[3]), pack2bf(v[4], v[5]), pack2bf(v[6], v[7]));
-    } else {
-      for (int j = 0; j < 8; ++j)
-        if (i + j < n) y[i + j] = f2bf(v[j]);
-    }
-  } else {
-    float* y = (float*)p;
-    if (i + 8 <= n) {
-      *(float4*)(y + i) = make_float4(v[0], v[1], v[2], v[3]);
-      *(float4*)(y + i + 4) = make_float4(v[4], v[5], v[6], v[7]);
-    } else {
-      for (int j = 0; j < 8; ++j)
-        if (i + j < n) y[i + j] = v[j];
+  if (i + 8 <= n) {
+    st8<BF16>(p, (size_t)i, v);
+    return;
+  }
+  for (int j = 0; j < 8; ++j) {
+    if (i + j < n) {
+      if (BF16) ((bf16_t*)p)[i + j] = f2bf(v[j]);
+      else ((float*)p)[i + j] = v[j];
     }
   }
 }

@@ -10,7 +10,7 @@
 //   * moving_x -= (moving_x - batch_x) * (1 - decay).
 // Activations are processed 8 channels (16 B) per lane; per-channel partial sums are reduced
 // through LDS and committed with one fp32 atomic per channel per block.
-#include "common.h"
+#include "nhwc8.h"
 
 namespace dtm {
 
@@ -25,13 +25,8 @@ struct Vec<8> {
     uint32_t w = e < 2 ? u.x : e < 4 ? u.y : e < 6 ? u.z : u.w;
     return (e & 1) ? hi_bf(w) : lo_bf(w);
   }
-  __device__ __forceinline__ void unpack(float* f) const {
-    f[0] = lo_bf(u.x); f[1] = hi_bf(u.x); f[2] = lo_bf(u.y); f[3] = hi_bf(u.y);
-    f[4] = lo_bf(u.z); f[5] = hi_bf(u.z); f[6] = lo_bf(u.w); f[7] = hi_bf(u.w);
-  }
-  __device__ __forceinline__ void pack(const float* f) {
-    u = make_uint4(pack2bf(f[0], f[1]), pack2bf(f[2], f[3]), pack2bf(f[4], f[5]), pack2bf(f[6], f[7]));
-  }
+  __device__ __forceinline__ void unpack(float* f) const { unpack8(u, f); }
+  __device__ __forceinline__ void pack(const float* f) { u = pack8(f); }
 };
 template <>
 struct Vec<1> {
@@ -294,14 +289,6 @@ __global__ void bn_param_grad_kernel(const float* __restrict__ sums, float* __re
 // rows with stride 256/(C/8); U independent 16-B loads are in flight per lane.
 constexpr int FU = 4;
 
-__device__ __forceinline__ void unpack8(uint4 u, float* f) {
-  f[0] = lo_bf(u.x); f[1] = hi_bf(u.x); f[2] = lo_bf(u.y); f[3] = hi_bf(u.y);
-  f[4] = lo_bf(u.z); f[5] = hi_bf(u.z); f[6] = lo_bf(u.w); f[7] = hi_bf(u.w);
-}
-__device__ __forceinline__ uint4 pack8(const float* f) {
-  return make_uint4(pack2bf(f[0], f[1]), pack2bf(f[2], f[3]), pack2bf(f[4], f[5]), pack2bf(f[6], f[7]));
-}
-
 
 __global__ __launch_bounds__(256) void bn_stats_fast(const bf16_t* __restrict__ x, float* __restrict__ stats, int M,
                                                      int C, int rpb) {
@@ -330,15 +317,6 @@ __global__ __launch_bounds__(256) void bn_stats_fast(const bf16_t* __restrict__ 
 
 // mask (optional, relu only): one bit per output element, bit e of byte (row*C + c0)/8 = [y > 0] for
 // channel c0+e -- the ReLU mask the backward needs, 1/16 of the bytes of y.
-typedef unsigned int v4u_bn_t __attribute__((ext_vector_type(4)));
-template <bool NT>
-__device__ __forceinline__ uint4 ld16_bn(const bf16_t* p) {
-  if (NT) {
-    v4u_bn_t v = __builtin_nontemporal_load((const v4u_bn_t*)p);
-    return make_uint4(v.x, v.y, v.z, v.w);
-  }
-  return *(const uint4*)p;
-}
 
 template <bool NT>
 __global__ __launch_bounds__(256) void bn_apply_fast(const bf16_t* __restrict__ x, const float* __restrict__ ss,
@@ -360,8 +338,8 @@ __global__ __launch_bounds__(256) void bn_apply_fast(const bf16_t* __restrict__ 
     for (int u = 0; u < FU; ++u) {
       int rr = r + u * RP;
       bool ok = rr < r1;
-      v[u] = ok ? ld16_bn<NT>(x + (size_t)rr * C + c0) : make_uint4(0, 0, 0, 0);
-      if (res_mode) w[u] = ok ? ld16_bn<NT>(res + (size_t)rr * C + c0) : make_uint4(0, 0, 0, 0);
+      v[u] = ok ? ld16<NT>(x + (size_t)rr * C + c0) : make_uint4(0, 0, 0, 0);
+      if (res_mode) w[u] = ok ? ld16<NT>(res + (size_t)rr * C + c0) : make_uint4(0, 0, 0, 0);
     }
 #pragma unroll
     for (int u = 0; u < FU; ++u) {

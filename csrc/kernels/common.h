@@ -104,55 +104,6 @@ int dtm_bn_stats_finalize(const float* ws, int rows, int K, const float* gamma, 
                           float* mov_var, float* ss, float count, float eps, float decay, int update, int bessel,
                           hipStream_t st);
 
-// Column-fixed lane mapping used by the BN kernels: lane t owns channel block (t % cols) * 8 and
-// row-lane t / cols; with RP = 256 / cols row-lanes, lanes >= RP*cols idle (C/8 need not divide 256).
-// col_reduce8 sums the per-lane [8] partials of the RP row-lanes of each column in LDS and writes
-// the per-block partial row out0[c0..c0+7], out1[...] (plain stores; reduced later by reduce_rows).
-// atomic: add into the final [C] sums instead (small grids: one launch fewer, <= a few hundred
-// adders per address).
-template <int NT = 256>
-__device__ __forceinline__ void col_reduce8(float (*red)[NT][8], const float* s, const float* q, float* out0,
-                                            float* out1, int cols, int c0, bool atomic = false) {
-  const int t = threadIdx.x, RP = NT / cols;  // (NT: the red table's rows; blocks of cols * (NT / cols) lanes)
-  if (RP == 1) {
-    if (t < cols) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        if (atomic) { atomicAdd(out0 + c0 + e, s[e]); atomicAdd(out1 + c0 + e, q[e]); }
-        else { out0[c0 + e] = s[e]; out1[c0 + e] = q[e]; }
-      }
-    }
-    return;
-  }
-  __syncthreads();  // red may still be read by a previous call
-#pragma unroll
-  for (int e = 0; e < 8; ++e) { red[0][t][e] = s[e]; red[1][t][e] = q[e]; }
-  __syncthreads();
-  int P = 1;
-  while (P * 2 <= RP) P *= 2;
-  if (P < RP) {  // fold the row-lanes beyond the largest power of two
-    if (t < (RP - P) * cols) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) { red[0][t][e] += red[0][t + P * cols][e]; red[1][t][e] += red[1][t + P * cols][e]; }
-    }
-    __syncthreads();
-  }
-  for (int h = P / 2; h >= 1; h >>= 1) {
-    if (t < h * cols) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) { red[0][t][e] += red[0][t + h * cols][e]; red[1][t][e] += red[1][t + h * cols][e]; }
-    }
-    __syncthreads();
-  }
-  if (t < cols) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      if (atomic) { atomicAdd(out0 + c0 + e, red[0][t][e]); atomicAdd(out1 + c0 + e, red[1][t][e]); }
-      else { out0[c0 + e] = red[0][t][e]; out1[c0 + e] = red[1][t][e]; }
-    }
-  }
-}
-
 namespace dtm {
 // BatchNorm finalize backward of one channel (bn_finalize_bwd_kernel's algebra): from dss = [dscale;
 // dshift; dmean; drstd], ss = [scale; shift; mean; rstd] and gamma -> the statistics gradient

@@ -7,22 +7,13 @@
 //   fwd:   y[n,p,q,c*M+m] = sum_{r,s} x[n, p*st-ph+r*d, q*st-pw+s*d, c] * w[r,s,c,m]
 //   dgrad: gather over the taps that touched (h, w)
 //   wgrad: per-block partial sums over pixels for all R*S taps, then the two-stage row reduction.
-#include "common.h"
+#include "nhwc8.h"
 
 namespace dtm {
 
 struct DwArgs {
   int N, H, W, C, M, R, S, P, Q, stride, ph, pw, dil;
 };
-
-__device__ __forceinline__ void ld8(const bf16_t* p, float* f) {
-  uint4 u = *(const uint4*)p;
-  f[0] = lo_bf(u.x); f[1] = hi_bf(u.x); f[2] = lo_bf(u.y); f[3] = hi_bf(u.y);
-  f[4] = lo_bf(u.z); f[5] = hi_bf(u.z); f[6] = lo_bf(u.w); f[7] = hi_bf(u.w);
-}
-__device__ __forceinline__ void st8(bf16_t* p, const float* f) {
-  *(uint4*)p = make_uint4(pack2bf(f[0], f[1]), pack2bf(f[2], f[3]), pack2bf(f[4], f[5]), pack2bf(f[6], f[7]));
-}
 
 __global__ __launch_bounds__(256) void dw_fwd8(const bf16_t* __restrict__ x, const float* __restrict__ w,
                                                bf16_t* __restrict__ y, DwArgs a) {
@@ -42,13 +33,13 @@ __global__ __launch_bounds__(256) void dw_fwd8(const bf16_t* __restrict__ x, con
         int ww = q * a.stride - a.pw + s * a.dil;
         if (ww < 0 || ww >= a.W) continue;
         float xv[8];
-        ld8(x + (((long)n * a.H + h) * a.W + ww) * a.C + c0, xv);
+        ld8<true>(x, (((long)n * a.H + h) * a.W + ww) * a.C + c0, xv);
         const float* wp = w + ((long)r * a.S + s) * a.C + c0;
 #pragma unroll
         for (int e = 0; e < 8; ++e) acc[e] += xv[e] * wp[e];
       }
     }
-    st8(y + o * a.C + c0, acc);
+    st8<true>(y, o * a.C + c0, acc);
   }
 }
 
@@ -74,13 +65,13 @@ __global__ __launch_bounds__(256) void dw_dgrad8(const bf16_t* __restrict__ dy, 
         int q = pq / a.stride;
         if (q >= a.Q) continue;
         float g[8];
-        ld8(dy + (((long)n * a.P + p) * a.Q + q) * a.C + c0, g);
+        ld8<true>(dy, (((long)n * a.P + p) * a.Q + q) * a.C + c0, g);
         const float* wp = w + ((long)r * a.S + s) * a.C + c0;
 #pragma unroll
         for (int e = 0; e < 8; ++e) acc[e] += g[e] * wp[e];
       }
     }
-    st8(dx + o * a.C + c0, acc);
+    st8<true>(dx, o * a.C + c0, acc);
   }
 }
 
@@ -105,8 +96,8 @@ __global__ __launch_bounds__(256) void dw_wgrad8(const bf16_t* __restrict__ x, c
           int h = p * a.stride - a.ph + r * a.dil, ww = q * a.stride - a.pw + s * a.dil;
           if (h < 0 || h >= a.H || ww < 0 || ww >= a.W) continue;
           float xv[8], g[8];
-          ld8(x + (((long)n * a.H + h) * a.W + ww) * a.C + c0, xv);
-          ld8(dy + m * a.C + c0, g);
+          ld8<true>(x, (((long)n * a.H + h) * a.W + ww) * a.C + c0, xv);
+          ld8<true>(dy, m * a.C + c0, g);
 #pragma unroll
           for (int e = 0; e < 8; ++e) acc[e] += xv[e] * g[e];
         }

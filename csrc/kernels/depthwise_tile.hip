@@ -45,7 +45,7 @@
 //   dwt_conv<3,2>             73      0    dwt_wgrad<3,2>            81      0
 //   dwt_conv<7,2>            127      0    dwt_wgrad<7,2>           113      0
 //   dwt_dgrad2<3>            70       0    dwt_dgrad2<7>            83       0
-#include "common.h"
+#include "nhwc8.h"
 
 namespace dtm {
 
@@ -73,14 +73,6 @@ struct WgP {
   int U;                          // pixel lanes
   FastDiv d_cpb, d_xrow, d_dyrow, d_R;
 };
-
-__device__ __forceinline__ void unpack8(uint4 u, float* f) {
-  f[0] = lo_bf(u.x); f[1] = hi_bf(u.x); f[2] = lo_bf(u.y); f[3] = hi_bf(u.y);
-  f[4] = lo_bf(u.z); f[5] = hi_bf(u.z); f[6] = lo_bf(u.w); f[7] = hi_bf(u.w);
-}
-__device__ __forceinline__ void store8(bf16_t* p, const float* f) {
-  *(uint4*)p = make_uint4(pack2bf(f[0], f[1]), pack2bf(f[2], f[3]), pack2bf(f[4], f[5]), pack2bf(f[6], f[7]));
-}
 
 // Stage the [rows][wcols] pixel window at (r0, c0) of one image (IH x IW x C, channels ch0 .. ch0 + cb*8) into
 // lds[row * pitch + col * cpb + column]; pixels outside the image are zero, columns >= cb are left alone (no lane
@@ -162,7 +154,7 @@ __global__ __launch_bounds__(256) void dwt_conv(const bf16_t* __restrict__ in, c
   bf16_t* o = out + (((long)n * p.OH + oh) * p.OW + ow) * p.C + ch0 + cg * 8;
 #pragma unroll
   for (int j = 0; j < 4; ++j)
-    if (ow + j < p.OW) store8(o + (long)j * p.C, acc[j]);
+    if (ow + j < p.OW) st8<true>(o, (long)j * p.C, acc[j]);
 }
 
 // dgrad at stride 2.  p.IH x p.IW is dy (P x Q), p.OH x p.OW is dx (H x W); p.ph / p.pw are the forward pads.
@@ -221,7 +213,7 @@ __global__ __launch_bounds__(256) void dwt_dgrad2(const bf16_t* __restrict__ dy,
 #pragma unroll
   for (int j = 0; j < 4; ++j)
     if (ow + j >= 0 && ow + j < p.OW)
-      store8(dx + (((long)n * p.OH + oh) * p.OW + ow + j) * p.C + ch0 + cg * 8, acc[j]);
+      st8<true>(dx, (((long)n * p.OH + oh) * p.OW + ow + j) * p.C + ch0 + cg * 8, acc[j]);
 }
 
 template <int S, int ST>

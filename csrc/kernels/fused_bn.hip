@@ -12,39 +12,11 @@
 // Lane mapping: one fixed 8-channel column per lane (parameters in registers), 16-B accesses.
 #include <cstring>
 
-#include "common.h"
+#include "nhwc8.h"
 
 namespace dtm {
 
 constexpr int FU2 = 4;
-
-__device__ __forceinline__ void up8(uint4 u, float* f) {
-  f[0] = lo_bf(u.x); f[1] = hi_bf(u.x); f[2] = lo_bf(u.y); f[3] = hi_bf(u.y);
-  f[4] = lo_bf(u.z); f[5] = hi_bf(u.z); f[6] = lo_bf(u.w); f[7] = hi_bf(u.w);
-}
-__device__ __forceinline__ uint4 pk8(const float* f) {
-  return make_uint4(pack2bf(f[0], f[1]), pack2bf(f[2], f[3]), pack2bf(f[4], f[5]), pack2bf(f[6], f[7]));
-}
-
-
-typedef unsigned int v4u_t __attribute__((ext_vector_type(4)));
-template <bool NT>
-__device__ __forceinline__ uint4 ld16(const bf16_t* p) {
-  if (NT) {
-    v4u_t v = __builtin_nontemporal_load((const v4u_t*)p);
-    return make_uint4(v.x, v.y, v.z, v.w);
-  }
-  return *(const uint4*)p;
-}
-template <bool NT>
-__device__ __forceinline__ void st16(bf16_t* p, uint4 u) {
-  if (NT) {
-    v4u_t v = {u.x, u.y, u.z, u.w};
-    __builtin_nontemporal_store(v, (v4u_t*)p);
-  } else {
-    *(uint4*)p = u;
-  }
-}
 
 // y = act(x) path backward.  mode: 0 = plain BN (no relu), 1 = relu with mask from y, 2 = relu with
 // mask recomputed from x*scale+shift.  res_mode 0/1/2 as in bn_apply.
@@ -96,9 +68,9 @@ __global__ __launch_bounds__(256) void bn_apply_bwd_kernel(const bf16_t* __restr
       if (rr >= r1) break;
       size_t o = (size_t)rr * C + c0;
       float g[8], xv[8];
-      up8(vdy[u], g); up8(vx[u], xv);
+      unpack8(vdy[u], g); unpack8(vx[u], xv);
       if (mode == 1) {
-        float yv[8]; up8(vy[u], yv);
+        float yv[8]; unpack8(vy[u], yv);
 #pragma unroll
         for (int e = 0; e < 8; ++e) g[e] = yv[e] > 0.f ? g[e] : 0.f;
       } else if (mode == 2) {
@@ -111,29 +83,29 @@ __global__ __launch_bounds__(256) void bn_apply_bwd_kernel(const bf16_t* __restr
 #pragma unroll
       for (int e = 0; e < 8; ++e) { a1[e] += g[e] * xv[e]; a0[e] += g[e]; }
       if (res_mode == 2) {
-        float rv[8]; up8(vr[u], rv);
+        float rv[8]; unpack8(vr[u], rv);
 #pragma unroll
         for (int e = 0; e < 8; ++e) { b1[e] += g[e] * rv[e]; b0[e] += g[e]; }
       }
       if (ux) {
-        *(uint4*)(dx + o) = pk8(g);
+        *(uint4*)(dx + o) = pack8(g);
       } else {
         float d[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) d[e] = g[e] * sc[e];
-        *(uint4*)(dx + o) = pk8(d);
+        *(uint4*)(dx + o) = pack8(d);
       }
       // dres: skipped when it equals dx (the caller aliases the two)
       if (res_mode == 1 && !ux) {
-        *(uint4*)(dres + o) = pk8(g);
+        *(uint4*)(dres + o) = pack8(g);
       } else if (res_mode == 2 && !(ux && ur)) {
         if (ur) {
-          *(uint4*)(dres + o) = pk8(g);
+          *(uint4*)(dres + o) = pack8(g);
         } else {
           float dr[8];
 #pragma unroll
           for (int e = 0; e < 8; ++e) dr[e] = g[e] * rsc[e];
-          *(uint4*)(dres + o) = pk8(dr);
+          *(uint4*)(dres + o) = pack8(dr);
         }
       }
     }
@@ -173,10 +145,10 @@ __global__ __launch_bounds__(256) void stats_combine_kernel(const bf16_t* __rest
       int rr = row + u * RP;
       if (rr >= r1) break;
       float d[8], xv[8];
-      up8(vd[u], d); up8(vx[u], xv);
+      unpack8(vd[u], d); unpack8(vx[u], xv);
 #pragma unroll
       for (int e = 0; e < 8; ++e) d[e] += a[e] + b[e] * xv[e];
-      *(uint4*)(out + (size_t)rr * C + c0) = pk8(d);
+      *(uint4*)(out + (size_t)rr * C + c0) = pack8(d);
     }
   }
 }
@@ -227,10 +199,10 @@ __global__ __launch_bounds__(256) void stats_combine_fin_kernel(const bf16_t* __
       int rr = row + u * RP;
       if (rr >= r1) break;
       float d[8], xv[8];
-      up8(vd[u], d); up8(vx[u], xv);
+      unpack8(vd[u], d); unpack8(vx[u], xv);
 #pragma unroll
       for (int e = 0; e < 8; ++e) d[e] = fmaf(d[e], sc[e], a[e] + b[e] * xv[e]);
-      st16<NTS>(out + (size_t)rr * ldo + c0, pk8(d));  // (ldo > C: a column slice of a wider buffer)
+      st16<NTS>(out + (size_t)rr * ldo + c0, pack8(d));  // (ldo > C: a column slice of a wider buffer)
     }
   }
 }
@@ -319,7 +291,7 @@ __global__ __launch_bounds__(256) void cat_bn_apply_kernel(CatArgs a, bf16_t* __
         continue;
       }
       float f[8];
-      up8(v[u], f);
+      unpack8(v[u], f);
       uint32_t bits = 0u;
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
@@ -327,7 +299,7 @@ __global__ __launch_bounds__(256) void cat_bn_apply_kernel(CatArgs a, bf16_t* __
         if (relu) f[e] = fmaxf(f[e], 0.f);
         bits |= (f[e] > 0.f ? 1u : 0u) << e;
       }
-      *(uint4*)(out + (size_t)rr * a.Ct + gc) = pk8(f);
+      *(uint4*)(out + (size_t)rr * a.Ct + gc) = pack8(f);
       if (P.mask) P.mask[((size_t)rr * P.C + cl) >> 3] = (uint8_t)bits;
     }
   }
@@ -374,8 +346,8 @@ __global__ __launch_bounds__(NT) void cat_bn_apply_bwd_kernel(CatArgs a, const b
       const int rr = row + u * RP;
       if (rr >= r1) break;
       float g[8], xv[8];
-      up8(vd[u], g);
-      up8(vx[u], xv);
+      unpack8(vd[u], g);
+      unpack8(vx[u], xv);
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         g[e] = (mb[u] >> e) & 1u ? g[e] : 0.f;
@@ -383,7 +355,7 @@ __global__ __launch_bounds__(NT) void cat_bn_apply_bwd_kernel(CatArgs a, const b
         a0[e] += g[e];
         if (!ux) g[e] *= sc[e];
       }
-      *(uint4*)(P.dx + (size_t)rr * P.C + cl) = pk8(g);
+      *(uint4*)(P.dx + (size_t)rr * P.C + cl) = pack8(g);
     }
   }
   float* row = ws + (size_t)blockIdx.x * 4 * a.Ct + 4 * P.off;  // this part's [4][C] image in the row
@@ -626,10 +598,10 @@ __global__ __launch_bounds__(256) void stats_combine_multi_kernel(CombGroup grp,
       const int rr = row + u * RP;
       if (rr >= r1) break;
       float d[8], xv[8];
-      up8(vd[u], d); up8(vx[u], xv);
+      unpack8(vd[u], d); unpack8(vx[u], xv);
 #pragma unroll
       for (int e = 0; e < 8; ++e) d[e] = fmaf(d[e], sc[e], a[e] + b[e] * xv[e]);
-      *(uint4*)(o + (size_t)rr * ldo + c0) = pk8(d);
+      *(uint4*)(o + (size_t)rr * ldo + c0) = pack8(d);
     }
   }
 }

@@ -20,7 +20,7 @@
 //           gn_bwd_apply_kernel  merges the group records, slab 0 stores sums[n][c], all write
 //                                dx = rstd * (gamma_c * dy - A_g/m - xhat * B_g/m);
 //           gn_bwd_param_kernel  dbeta_c = sum_n sums[n][c][0], dgamma_c = sum_n sums[n][c][1], in n order.
-#include "common.h"
+#include "nhwc8.h"
 
 // Products and sums are fused only where fmaf says so: the backward's ReLU mask repeats the forward's roundings, and
 // gamma * dy minus its own group mean is exactly 0 for a group of one value.
@@ -36,30 +36,6 @@ struct GnGeom {
   int HW, C, G, Cg, C8, SP, slabs;
   int lg;  // log2(Cg) for Cg < 8
 };
-
-template <bool BF16>
-__device__ __forceinline__ void ld8(const void* p, size_t i, float (&v)[8]) {
-  if (BF16) {
-    const uint4 u = *(const uint4*)((const bf16_t*)p + i);
-    const uint32_t w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { v[2 * j] = lo_bf(w[j]); v[2 * j + 1] = hi_bf(w[j]); }
-  } else {
-    const float4 a = *(const float4*)((const float*)p + i), b = *(const float4*)((const float*)p + i + 4);
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-  }
-}
-
-template <bool BF16>
-__device__ __forceinline__ void st8(void* p, size_t i, const float (&v)[8]) {
-  if (BF16) {
-    *(uint4*)((bf16_t*)p + i) =
-        make_uint4(pack2bf(v[0], v[1]), pack2bf(v[2], v[3]), pack2bf(v[4], v[5]), pack2bf(v[6], v[7]));
-  } else {
-    *(float4*)((float*)p + i) = make_float4(v[0], v[1], v[2], v[3]);
-    *(float4*)((float*)p + i + 4) = make_float4(v[4], v[5], v[6], v[7]);
-  }
-}
 
 // (u, v) of na values absorbs (ub, vb) of nb values.  CHAN: (mean, M2) by Chan's formula; else plain sums.
 template <bool CHAN>
@@ -78,22 +54,6 @@ __device__ __forceinline__ void merge2(float& u, float& v, float na, float ub, f
 __device__ __forceinline__ void affine_ab(float mean, float rstd, float gm, float bt, float& a, float& b) {
   a = __fmul_rn(rstd, gm);
   b = __fmaf_rn(-mean, a, bt);
-}
-
-struct Chunk {
-  int c0, cc, PL, col, pl, c;
-  bool live;
-};
-__device__ __forceinline__ Chunk make_chunk(int c0, int C8) {
-  Chunk k;
-  k.c0 = c0;
-  k.cc = min(GN_T, C8 - c0);
-  k.PL = GN_T / k.cc;
-  k.col = threadIdx.x % k.cc;
-  k.pl = threadIdx.x / k.cc;
-  k.live = k.pl < k.PL;  // GN_T need not be a multiple of cc
-  k.c = (c0 + k.col) * 8;
-  return k;
 }
 
 // groups that the columns [c0, c0 + cc) touch: first group and their number (<= GN_GMAX)
@@ -207,7 +167,7 @@ __global__ __launch_bounds__(GN_T) void gn_stats_kernel(const void* __restrict__
   const size_t base = (size_t)n * g.HW * g.C;
   float* rec = ws + ((size_t)n * g.slabs + slab) * g.G * 2;
   for (int c0 = 0; c0 < g.C8; c0 += GN_T) {
-    const Chunk k = make_chunk(c0, g.C8);
+    const Chunk k = make_chunk<GN_T>(c0, g.C8);
     float K[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // the shift: this column at the slab's first pixel
     float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, q[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     if (k.live) {
@@ -250,7 +210,7 @@ __global__ __launch_bounds__(GN_T) void gn_apply_kernel(const void* __restrict__
   const size_t base = (size_t)n * g.HW * g.C;
   const float m = (float)g.HW * (float)g.Cg;
   for (int c0 = 0; c0 < g.C8; c0 += GN_T) {
-    const Chunk k = make_chunk(c0, g.C8);
+    const Chunk k = make_chunk<GN_T>(c0, g.C8);
     int gb, ng;
     chunk_groups(g, k, gb, ng);
     fold_slabs<true>(ws + (size_t)n * g.slabs * g.G * 2, (size_t)g.G * 2, g, gb, ng, gM, gR);
@@ -302,7 +262,7 @@ __global__ __launch_bounds__(GN_T) void gn_bwd_sums_kernel(const void* __restric
   const size_t base = (size_t)n * g.HW * g.C;
   float* row = ws + ((size_t)n * g.slabs + slab) * bwd_row(g);
   for (int c0 = 0; c0 < g.C8; c0 += GN_T) {
-    const Chunk k = make_chunk(c0, g.C8);
+    const Chunk k = make_chunk<GN_T>(c0, g.C8);
     float sg[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, sx[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     float gm[8];
     if (k.live) {
@@ -356,7 +316,7 @@ __global__ __launch_bounds__(GN_T) void gn_bwd_apply_kernel(const void* __restri
   const float inv_m = 1.f / ((float)g.HW * (float)g.Cg);
   const float* rows = ws + (size_t)n * g.slabs * bwd_row(g);
   for (int c0 = 0; c0 < g.C8; c0 += GN_T) {
-    const Chunk k = make_chunk(c0, g.C8);
+    const Chunk k = make_chunk<GN_T>(c0, g.C8);
     int gb, ng;
     chunk_groups(g, k, gb, ng);
     fold_slabs<false>(rows + 2 * (size_t)g.C, bwd_row(g), g, gb, ng, gA, gB);

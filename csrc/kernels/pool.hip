@@ -14,7 +14,7 @@
 //     VALID avg pool, the 8-channel global mean fwd, the BN+ReLU max-pool gather bwd, 3x3/2 max pools, 3x3/1 avg
 //     pools.  They hold their results bit-identical to the generic bodies (tests/test_kernels_gpu.py);
 //  4. host dispatch: fits32 / k3s2_ok / k3s1_ok pick the kernel, one launch wrapper per generic body.
-#include "common.h"
+#include "nhwc8.h"
 
 namespace dtm {
 
@@ -24,11 +24,6 @@ struct PoolArgs {
 // first window index p >= 0 with p*S >= num  (num = h + pad - k + 1)
 __device__ __forceinline__ int first_win(int num, int S) { return num <= 0 ? 0 : (num + S - 1) / S; }
 
-// eight bf16 of a 16-B chunk as floats, in memory order
-__device__ __forceinline__ void unpack8(uint4 u, float* f) {
-  f[0] = lo_bf(u.x); f[1] = hi_bf(u.x); f[2] = lo_bf(u.y); f[3] = hi_bf(u.y);
-  f[4] = lo_bf(u.z); f[5] = hi_bf(u.z); f[6] = lo_bf(u.w); f[7] = hi_bf(u.w);
-}
 __device__ __forceinline__ void add8(float* acc, uint4 u) {
   float f[8];
   unpack8(u, f);
@@ -50,16 +45,13 @@ __device__ __forceinline__ uint32_t arg_byte(uint2 v, int e) { return ((e < 4 ? 
 
 template <int V>
 __device__ __forceinline__ void ld(const bf16_t* p, float* f) {
-  if constexpr (V == 8) unpack8(*(const uint4*)p, f);
+  if constexpr (V == 8) ld8<true>(p, 0, f);
   else f[0] = bf2f(*p);
 }
 template <int V>
 __device__ __forceinline__ void st(bf16_t* p, const float* f) {
-  if constexpr (V == 8) {
-    *(uint4*)p = make_uint4(pack2bf(f[0], f[1]), pack2bf(f[2], f[3]), pack2bf(f[4], f[5]), pack2bf(f[6], f[7]));
-  } else {
-    *p = f2bf(f[0]);
-  }
+  if constexpr (V == 8) st8<true>(p, 0, f);
+  else *p = f2bf(f[0]);
 }
 
 // ---- index policies: how a kernel divides its flat index.  Idx32: 32-bit magic-number division (every index below

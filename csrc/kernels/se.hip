@@ -7,7 +7,7 @@
 // Work split of the passes over the big tensors, as groupnorm.hip: a sample's pixels are cut into slabs of
 // slab_pixels consecutive pixels, the grid is (slabs, N); lane t owns the 16-byte column t % cols and the pixel lane
 // t / cols (cols = C/8, in chunks of 256 columns when C/8 > 256), so every trip reads one contiguous run.  Pixel lanes
-// are summed through LDS by col_sum8's fixed tree, slab records are merged in slab order.  The excitation MLP runs in
+// are summed through LDS by col_tree8's fixed tree, slab records are merged in slab order.  The excitation MLP runs in
 // blocks of 1024 lanes, one per SE_G consecutive samples: a weight row loaded once serves the whole sample group, whose
 // squeezed vectors live in LDS.  No atomics, no flags, no waiting between blocks: every result keeps its bits.
 //
@@ -20,7 +20,7 @@
 //           se_gate_bwd_kernel  merges to dg;  da2 = dg g (1 - g);  dz = (w2^T da2) [z > 0];  ds = (w1^T dz) / HW;
 //           se_wgrad_kernel     dw2 = sum_n da2 (x) z, db2 = sum_n da2, dw1 = sum_n dz (x) s, db1 = sum_n dz;
 //           se_bwd_apply_kernel dx = dm * g + ds;  dresidual = dm (written only where it is not dy itself).
-#include "common.h"
+#include "nhwc8.h"
 
 namespace dtm {
 namespace {
@@ -37,68 +37,20 @@ struct SeGeom {
   int N, HW, C, C8, Cr, SP, slabs;
 };
 
-__device__ __forceinline__ void ld8(const bf16_t* p, size_t i, float (&v)[8]) {
-  const uint4 u = *(const uint4*)(p + i);
-  const uint32_t w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-  for (int j = 0; j < 4; ++j) { v[2 * j] = lo_bf(w[j]); v[2 * j + 1] = hi_bf(w[j]); }
-}
-__device__ __forceinline__ void st8(bf16_t* p, size_t i, const float (&v)[8]) {
-  *(uint4*)(p + i) = make_uint4(pack2bf(v[0], v[1]), pack2bf(v[2], v[3]), pack2bf(v[4], v[5]), pack2bf(v[6], v[7]));
-}
-__device__ __forceinline__ void ldf8(const float* p, float (&v)[8]) {
-  const float4 a = *(const float4*)p, b = *(const float4*)(p + 4);
-  v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-}
-
-struct Chunk {
-  int cc, PL, pl, c;
-  bool live;
-};
-__device__ __forceinline__ Chunk make_chunk(int c0, int C8) {
-  Chunk k;
-  k.cc = min(SE_T, C8 - c0);
-  k.PL = SE_T / k.cc;
-  k.pl = threadIdx.x / k.cc;
-  k.live = k.pl < k.PL;  // SE_T need not be a multiple of cc
-  k.c = (c0 + threadIdx.x % k.cc) * 8;
-  return k;
-}
-
-// The [8] partials of the PL pixel lanes of each column are summed in LDS by a fixed tree; the lanes t < cols store
-// their column's totals at out (their own pointer).  Called by the whole block.
-__device__ __forceinline__ void col_sum8(float (*red)[8], const float (&s)[8], float* out, int cols) {
-  const int t = threadIdx.x, PL = SE_T / cols;
-  if (PL == 1) {
+// One accumulator set through col_tree8: the lanes t < cols store their column's totals at out (their own pointer).
+// Called by the whole block.
+__device__ __forceinline__ void col_sum8(float (*red)[SE_T][8], const float (&s)[8], float* out, int cols) {
+  const int t = threadIdx.x;
+  if (!col_tree8<1, SE_T>(red, s, nullptr, cols)) {
     if (t < cols) {
       *(float4*)out = make_float4(s[0], s[1], s[2], s[3]);
       *(float4*)(out + 4) = make_float4(s[4], s[5], s[6], s[7]);
     }
     return;
   }
-  __syncthreads();  // red may still be read by the previous chunk
-#pragma unroll
-  for (int e = 0; e < 8; ++e) red[t][e] = s[e];
-  __syncthreads();
-  int P = 1;
-  while (P * 2 <= PL) P *= 2;
-  if (P < PL) {  // fold the pixel lanes beyond the largest power of two
-    if (t < (PL - P) * cols) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) red[t][e] += red[t + P * cols][e];
-    }
-    __syncthreads();
-  }
-  for (int h = P / 2; h >= 1; h >>= 1) {
-    if (t < h * cols) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) red[t][e] += red[t + h * cols][e];
-    }
-    __syncthreads();
-  }
   if (t < cols) {
-    *(float4*)out = make_float4(red[t][0], red[t][1], red[t][2], red[t][3]);
-    *(float4*)(out + 4) = make_float4(red[t][4], red[t][5], red[t][6], red[t][7]);
+    *(float4*)out = make_float4(red[0][t][0], red[0][t][1], red[0][t][2], red[0][t][3]);
+    *(float4*)(out + 4) = make_float4(red[0][t][4], red[0][t][5], red[0][t][6], red[0][t][7]);
   }
 }
 
@@ -106,19 +58,19 @@ __device__ __forceinline__ void col_sum8(float (*red)[8], const float (&s)[8], f
 // ws[n][slab][c] = sum of x over the slab's pixels
 __global__ __launch_bounds__(SE_T) void se_squeeze_kernel(const bf16_t* __restrict__ x, float* __restrict__ ws,
                                                           SeGeom g) {
-  __shared__ float red[SE_T][8];
+  __shared__ float red[1][SE_T][8];
   const int n = blockIdx.y, slab = blockIdx.x;
   const int p0 = slab * g.SP, p1 = min(g.HW, p0 + g.SP);
   const size_t base = (size_t)n * g.HW * g.C;
   float* rec = ws + ((size_t)n * g.slabs + slab) * g.C;
   for (int c0 = 0; c0 < g.C8; c0 += SE_T) {
-    const Chunk k = make_chunk(c0, g.C8);
+    const Chunk k = make_chunk<SE_T>(c0, g.C8);
     float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     if (k.live) {
 #pragma unroll 4
       for (int p = p0 + k.pl; p < p1; p += k.PL) {
         float v[8];
-        ld8(x, base + (size_t)p * g.C + k.c, v);
+        ld8<true>(x, base + (size_t)p * g.C + k.c, v);
 #pragma unroll
         for (int e = 0; e < 8; ++e) s[e] += v[e];
       }
@@ -229,22 +181,22 @@ __global__ __launch_bounds__(SE_T) void se_scale_kernel(const bf16_t* __restrict
   const int p0 = slab * g.SP, p1 = min(g.HW, p0 + g.SP);
   const size_t base = (size_t)n * g.HW * g.C;
   for (int c0 = 0; c0 < g.C8; c0 += SE_T) {
-    const Chunk k = make_chunk(c0, g.C8);
+    const Chunk k = make_chunk<SE_T>(c0, g.C8);
     if (!k.live) continue;
     float gv[8];
-    ldf8(gate + (size_t)n * g.C + k.c, gv);
+    ld8<false>(gate + (size_t)n * g.C + k.c, 0, gv);
 #pragma unroll 2
     for (int p = p0 + k.pl; p < p1; p += k.PL) {
       const size_t off = base + (size_t)p * g.C + k.c;
       float v[8], r[8];
-      ld8(x, off, v);
-      if (RES) ld8(res, off, r);
+      ld8<true>(x, off, v);
+      if (RES) ld8<true>(res, off, r);
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         v[e] = RES ? fmaf(v[e], gv[e], r[e]) : v[e] * gv[e];
         if (RELU) v[e] = fmaxf(v[e], 0.f);
       }
-      st8(y, off, v);
+      st8<true>(y, off, v);
     }
   }
 }
@@ -254,22 +206,22 @@ template <bool RELU>
 __global__ __launch_bounds__(SE_T) void se_bwd_sums_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ y,
                                                            const bf16_t* __restrict__ dy, float* __restrict__ ws,
                                                            SeGeom g) {
-  __shared__ float red[SE_T][8];
+  __shared__ float red[1][SE_T][8];
   const int n = blockIdx.y, slab = blockIdx.x;
   const int p0 = slab * g.SP, p1 = min(g.HW, p0 + g.SP);
   const size_t base = (size_t)n * g.HW * g.C;
   float* rec = ws + ((size_t)n * g.slabs + slab) * g.C;
   for (int c0 = 0; c0 < g.C8; c0 += SE_T) {
-    const Chunk k = make_chunk(c0, g.C8);
+    const Chunk k = make_chunk<SE_T>(c0, g.C8);
     float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     if (k.live) {
 #pragma unroll 2
       for (int p = p0 + k.pl; p < p1; p += k.PL) {
         const size_t off = base + (size_t)p * g.C + k.c;
         float v[8], d[8], o[8];
-        ld8(x, off, v);
-        ld8(dy, off, d);
-        if (RELU) ld8(y, off, o);
+        ld8<true>(x, off, v);
+        ld8<true>(dy, off, d);
+        if (RELU) ld8<true>(y, off, o);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
           if (RELU && !(o[e] > 0.f)) d[e] = 0.f;
@@ -391,24 +343,24 @@ __global__ __launch_bounds__(SE_T) void se_bwd_apply_kernel(const bf16_t* __rest
   const int p0 = slab * g.SP, p1 = min(g.HW, p0 + g.SP);
   const size_t base = (size_t)n * g.HW * g.C;
   for (int c0 = 0; c0 < g.C8; c0 += SE_T) {
-    const Chunk k = make_chunk(c0, g.C8);
+    const Chunk k = make_chunk<SE_T>(c0, g.C8);
     if (!k.live) continue;
     float gv[8], sv[8];
-    ldf8(gate + (size_t)n * g.C + k.c, gv);
-    ldf8(ds + (size_t)n * g.C + k.c, sv);
+    ld8<false>(gate + (size_t)n * g.C + k.c, 0, gv);
+    ld8<false>(ds + (size_t)n * g.C + k.c, 0, sv);
 #pragma unroll 2
     for (int p = p0 + k.pl; p < p1; p += k.PL) {
       const size_t off = base + (size_t)p * g.C + k.c;
       float d[8], o[8], v[8];
-      ld8(dy, off, d);
-      if (RELU) ld8(y, off, o);
+      ld8<true>(dy, off, d);
+      if (RELU) ld8<true>(y, off, o);
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         if (RELU && !(o[e] > 0.f)) d[e] = 0.f;
         v[e] = fmaf(d[e], gv[e], sv[e]);
       }
-      st8(dx, off, v);
-      if (DRES) st8(dres, off, d);
+      st8<true>(dx, off, v);
+      if (DRES) st8<true>(dres, off, d);
     }
   }
 }

@@ -1,5 +1,6 @@
 // Activations, instance normalisation and reflect padding for the model-zoo call sites that are not
 // fused into a conv / BatchNorm kernel:
+//   * exact GELU (ConvNeXt's MLP; the fourth kind of dtm_act_fwd / dtm_act_bwd);
 //   * ReLU6 (MobileNet v1/v2: reference vgg/nets/mobilenet_v1.py:428-472 via slim arg_scope
 //     activation_fn=tf.nn.relu6), leaky ReLU (DCGAN discriminator, vgg/nets/dcgan.py:89), ELU;
 //   * instance normalisation + reflect padding (CycleGAN generator, vgg/nets/cyclegan.py:66-117,
@@ -11,17 +12,23 @@
 
 namespace dtm {
 
-enum ActKind { ACT_RELU6 = 0, ACT_LEAKY = 1, ACT_ELU = 2 };
+enum ActKind { ACT_RELU6 = 0, ACT_LEAKY = 1, ACT_ELU = 2, ACT_GELU = 3 };
+
+// exact GELU (Hendrycks & Gimpel 2016): y = x Phi(x), Phi(x) = (1 + erf(x / sqrt 2)) / 2; dy/dx = Phi(x) + x phi(x)
+__device__ __forceinline__ float gelu_cdf(float x) { return 0.5f * (1.f + erff(x * 0.70710678118654752f)); }
+__device__ __forceinline__ float gelu_pdf(float x) { return 0.39894228040143268f * expf(-0.5f * x * x); }
 
 __device__ __forceinline__ float act_f(float x, int kind, float alpha) {
   if (kind == ACT_RELU6) return fminf(fmaxf(x, 0.f), 6.f);
   if (kind == ACT_LEAKY) return x > 0.f ? x : alpha * x;
+  if (kind == ACT_GELU) return x * gelu_cdf(x);
   return x > 0.f ? x : expm1f(x);
 }
 // derivative from the forward input x (TF: relu6 grad is 1 on (0, 6), leaky alpha below 0, elu exp(x))
 __device__ __forceinline__ float act_d(float x, int kind, float alpha) {
   if (kind == ACT_RELU6) return (x > 0.f && x < 6.f) ? 1.f : 0.f;
   if (kind == ACT_LEAKY) return x > 0.f ? 1.f : alpha;
+  if (kind == ACT_GELU) return fmaf(x, gelu_pdf(x), gelu_cdf(x));
   return x > 0.f ? 1.f : expf(x);
 }
 

@@ -547,6 +547,49 @@ def layer_norm(inputs, center=True, scale=True, activation_fn=None, reuse=None, 
                       reuse=reuse, trainable=trainable, scope=scope, _default_scope="LayerNorm")
 
 
+@add_arg_scope
+def channel_layer_norm(inputs, center=True, scale=True, epsilon=1e-6, activation_fn=None, param_initializers=None,
+                       reuse=None, trainable=True, scope=None):
+    """LayerNorm over the channels of every pixel (or token) of ``[..., C]`` on its own: ConvNeXt's and a transformer
+    block's normaliser, where ``layer_norm`` above keeps TF-contrib's one set of statistics per sample.  Variables
+    <scope>/beta and <scope>/gamma, without a regularizer; HIP kernels on CUDA (layernorm.hip).  Not fake-quantised."""
+    from ..ops.layernorm import channel_layer_norm as _cln
+    if _store.quant is not None:
+        raise ValueError("channel_layer_norm: LayerNorm layers are not quantised; build the model without --quantize")
+    x = as_tensor(inputs)
+    C = x.shape[-1]
+    pi = param_initializers or {}
+    with variable_scope(scope, "LayerNorm", reuse=reuse):
+        beta = variable("beta", (C,), initializer=pi.get("beta", ("constant", 0.0)), trainable=trainable) \
+            if center else None
+        gamma = variable("gamma", (C,), initializer=pi.get("gamma", ("constant", 1.0)), trainable=trainable) \
+            if scale else None
+    return _act(_cln(x, gamma, beta, epsilon), activation_fn)
+
+
+@add_arg_scope
+def layer_scale_residual(shortcut, branch, init_value=1e-6, row_scale=None, trainable=True, scope=None, reuse=None):
+    """shortcut + (row_scale[n] * gamma[c]) * branch: the layer scale of Touvron et al. 2021 (variable <scope>/gamma,
+    constant ``init_value``, no regularizer) with the residual add in one pass; ``row_scale`` fp32 [N] or None is
+    stochastic depth's per-sample factor.  HIP kernels on CUDA (layernorm.hip).  Not fake-quantised."""
+    from ..ops.layernorm import scale_residual as _sres
+    if _store.quant is not None:
+        raise ValueError("layer_scale_residual: layer-scale layers are not quantised; build the model without "
+                         "--quantize")
+    x, r = as_tensor(shortcut), as_tensor(branch)
+    with variable_scope(scope, "LayerScale", reuse=reuse):
+        gamma = variable("gamma", (x.shape[-1],), initializer=("constant", float(init_value)), trainable=trainable)
+    if r.dtype != x.dtype:
+        r = r.to(x.dtype)
+    return _sres(x, r, gamma, row_scale)
+
+
+def gelu(x):
+    """Exact GELU (HIP kernel on CUDA, activation.hip)."""
+    from ..ops.activation import gelu as _gelu
+    return _gelu(as_tensor(x))
+
+
 def leaky_relu(x, alpha=0.2):
     from ..ops.activation import leaky_relu as _lrelu
     return _lrelu(as_tensor(x), alpha)

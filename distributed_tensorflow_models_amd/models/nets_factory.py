@@ -65,6 +65,13 @@ networks_map = {
     # BoTNet-50: ResNet-50 whose last stage attends over its pixels instead of convolving 3x3 (ops/attention.py)
     "botnet_50": _slim(slim_nets.resnext, 224, depth=50, cardinality=1, base_width=64, mhsa_heads=4,
                        scope="botnet_50"),
+    # ConvNeXt: channel LayerNorm, GELU and layer scale + residual (ops/layernorm.py, ops/activation.py)
+    "convnext_tiny": _slim(slim_nets.convnext, 224, depths=(3, 3, 9, 3), dims=(96, 192, 384, 768),
+                           scope="convnext_tiny"),
+    "convnext_small": _slim(slim_nets.convnext, 224, depths=(3, 3, 27, 3), dims=(96, 192, 384, 768),
+                            scope="convnext_small"),
+    "convnext_base": _slim(slim_nets.convnext, 224, depths=(3, 3, 27, 3), dims=(128, 256, 512, 1024),
+                           scope="convnext_base"),
     "cifar10_resnet_v2": lambda num_classes=10, resnet_size=32, **kw: resnet_official.CifarResNetV2(
         resnet_size, num_classes, **kw),
     "imagenet_resnet_v2": lambda num_classes=1001, resnet_size=50, **kw: resnet_official.ImagenetResNetV2(

@@ -216,6 +216,57 @@ def resnext(images, num_classes=1000, is_training=True, depth=50, cardinality=32
 
 
 # =============================================================================================
+# ConvNeXt (Liu et al. 2022, "A ConvNet for the 2020s"): depthwise 7x7, channel LayerNorm, an inverted 1x1 MLP with
+# GELU, layer scale and the residual; LayerNorm + 2x2 stride-2 convs between the stages
+def _convnext_block(x, dim, layer_scale_init, row_scale, scope):
+    with slim.variable_scope(scope):
+        r = slim.separable_conv2d(x, None, 7, depth_multiplier=1, stride=1, padding="SAME", scope="dwconv")
+        r = slim.channel_layer_norm(r, scope="LayerNorm")
+        r = slim.gelu(slim.conv2d(r, 4 * dim, 1, scope="pwconv1"))
+        r = slim.conv2d(r, dim, 1, scope="pwconv2")
+        return slim.layer_scale_residual(x, r, init_value=layer_scale_init, row_scale=row_scale, scope="LayerScale")
+
+
+def convnext(images, num_classes=1000, is_training=True, depths=(3, 3, 9, 3), dims=(96, 192, 384, 768),
+             drop_path_rate=0.0, layer_scale_init=1e-6, weight_decay=0.05, scope="convnext"):
+    """ConvNeXt: a 4x4 stride-4 stem conv with bias and channel LayerNorm; four stages of ``depths[i]`` blocks at
+    ``dims[i]`` channels with LayerNorm and a 2x2 stride-2 conv before stages 2 - 4; global average pool, LayerNorm and
+    the classifier.  Convs and the classifier carry biases, no normaliser and no activation of their own; only their
+    weights take ``weight_decay``.  ``drop_path_rate``: stochastic depth, growing linearly over the blocks up to this
+    rate, in training only, as a per-sample factor 0 or 1 / (1 - p) on the block's branch; at rate 0 no random number is
+    drawn.  End points: <scope>/stem, <scope>/stage1 .. stage4, <scope>/logits."""
+    ep = {}
+    total, done = sum(depths), 0
+    layers = [slim.conv2d, slim.separable_conv2d, slim.fully_connected]
+    with slim.arg_scope(layers, weights_regularizer=slim.l2_regularizer(weight_decay),
+                        weights_initializer=slim.truncated_normal_initializer(stddev=0.02), activation_fn=None,
+                        normalizer_fn=None):
+        with slim.variable_scope(scope) as vs:
+            net = slim.conv2d(images, dims[0], 4, stride=4, padding="VALID", scope="stem")
+            net = ep[vs + "/stem"] = slim.channel_layer_norm(net, scope="stem/LayerNorm")
+            for si, (n, dim) in enumerate(zip(depths, dims)):
+                with slim.variable_scope("stage%d" % (si + 1)):
+                    if si > 0:
+                        net = slim.channel_layer_norm(net, scope="downsample/LayerNorm")
+                        net = slim.conv2d(net, dim, 2, stride=2, padding="VALID", scope="downsample")
+                    for b in range(n):
+                        p = drop_path_rate * done / max(total - 1, 1)
+                        row_scale = None
+                        if is_training and p > 0.0:
+                            x = as_tensor(net)
+                            keep = torch.rand(x.shape[0], device=x.device) >= p
+                            row_scale = keep.float() / (1.0 - p)
+                        net = _convnext_block(net, dim, layer_scale_init, row_scale, "block%d" % (b + 1))
+                        done += 1
+                ep["%s/stage%d" % (vs, si + 1)] = net
+            net = F.global_avg_pool(net)
+            net = slim.channel_layer_norm(net, scope="head/LayerNorm")
+            net = ep[vs + "/logits"] = slim.fully_connected(net, num_classes, scope="logits")
+            ep["predictions"] = torch.softmax(as_tensor(net).float(), -1)
+    return net, ep
+
+
+# =============================================================================================
 # Inception v1 (vgg/nets/inception_v1.py:29-327)
 def _mixed_v1(net, name, b0, b1a, b1b, b2a, b2b, b3, conv5_name="Conv2d_0b_3x3"):
     with slim.variable_scope(name):

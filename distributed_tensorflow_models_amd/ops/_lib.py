@@ -48,7 +48,12 @@ _SIGS = {
     "dtm_groupnorm_ws_floats": (_L, [_I, _I, _I, _I, _I, _I]),
     "dtm_groupnorm_fwd": (_I, [_P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _F, _I, _I, _P]),
     "dtm_groupnorm_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
-    "dtm_se_ws_floats": (_L, [_I, _I, _I, _I, _I, _I]),
+    "dtm_cln_ws_floats": (_L, [_L, _I, _I, _I]),
+    "dtm_cln_fwd": (_I, [_P, _P, _P, _P, _P, _L, _I, _I, _F, _I, _P]),
+    "dtm_cln_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _I, _I, _P]),
+    "dtm_scale_residual_fwd": (_I, [_P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _P]),
+    "dtm_scale_residual_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _I, _I, _I, _I, _P]),
+    "dtm_se_ws_floats":(_L, [_I, _I, _I, _I, _I, _I]),
     "dtm_se_fwd": (_I, [_P] * 11 + [_L, _I, _I, _I, _I, _I, _I, _P]),
     "dtm_se_bwd": (_I, [_P] * 15 + [_L, _I, _I, _I, _I, _I, _I, _P]),
     "dtm_mhsa_fwd": (_I, [_P] * 5 + [_L, _L, _L, _I, _I, _I, _I, _F, _P]),

@@ -1,4 +1,4 @@
-"""ReLU6 / leaky ReLU / ELU, instance normalisation and reflect padding on the HIP path
+"""ReLU6 / leaky ReLU / ELU / exact GELU, instance normalisation and reflect padding on the HIP path
 (``csrc/kernels/activation.hip``).
 
 Call sites: MobileNet v1/v2 ReLU6 (reference vgg/nets/mobilenet_v1.py:428-472), the DCGAN
@@ -10,7 +10,7 @@ import torch
 
 from . import _lib
 
-KIND = {"relu6": 0, "leaky_relu": 1, "elu": 2}
+KIND = {"relu6": 0, "leaky_relu": 1, "elu": 2, "gelu": 3}
 
 
 def _gpu(x):
@@ -22,6 +22,8 @@ def _torch_act(x, kind, alpha):
         return torch.clamp(x, 0.0, 6.0)
     if kind == "leaky_relu":
         return torch.nn.functional.leaky_relu(x, alpha)
+    if kind == "gelu":
+        return torch.nn.functional.gelu(x)  # the exact (erf) form
     return torch.nn.functional.elu(x)
 
 
@@ -62,6 +64,11 @@ def leaky_relu(x, alpha=0.2):
 
 def elu(x):
     return activation(x, "elu")
+
+
+def gelu(x):
+    """Exact GELU, y = 0.5 x (1 + erf(x / sqrt 2))."""
+    return activation(x, "gelu")
 
 
 class _InstanceNormFn(torch.autograd.Function):

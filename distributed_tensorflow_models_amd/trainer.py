@@ -111,6 +111,13 @@ PRESETS = {
                      batch_size=256, lr=0.1, lr_scale_workers=True, decay_epochs=30.0, decay_factor=0.1,
                      optimizer="momentum", momentum=0.9, ema=None, wd_all=None, max_steps=1000, save_secs=600,
                      log_style="standard", max_to_keep=5, train_dir="/tmp/botnet50_train", data_dir=""),
+    # ConvNeXt-T (channel LayerNorm, GELU, layer scale: ops/layernorm.py) under LAMB, whose decay is decoupled as in
+    # the AdamW recipe this family is trained with (the model's weight_decay 0.05 on conv / FC weights); stochastic
+    # depth is left at the model's default 0.  Nobody here has trained this recipe to accuracy.
+    "convnext_tiny": dict(model="convnext_tiny", num_classes=1000, dataset="synthetic_imagenet", image_size=224,
+                          batch_size=256, lr=0.004, lr_scale_workers=False, decay_epochs=30.0, decay_factor=0.1,
+                          optimizer="lamb", ema=None, wd_all=None, max_steps=1000, save_secs=600,
+                          log_style="standard", max_to_keep=5, train_dir="/tmp/convnext_tiny_train", data_dir=""),
     # BASELINE config #1 plumbing: LeNet on synthetic MNIST
     "lenet": dict(model="lenet", num_classes=10, dataset="synthetic_mnist", image_size=28, batch_size=64, lr=0.01,
                   lr_scale_workers=True, decay_epochs=100.0, decay_factor=0.1, optimizer="sgd", ema=None,

@@ -1,4 +1,6 @@
-"""Numerics of the HIP kernels against plain PyTorch fp32 references (GPU only)."""
+"""Numerics of the HIP kernels against plain PyTorch fp32 references (GPU only).
+The per-element checks of BatchNorm, the pools and LRN against float64 are in tests/test_norm_pool_gpu.py
+(references and bounds: tests/norm_pool_cases.py, checked on the CPU by tests/test_norm_pool_cpu.py)."""
 import pytest
 import torch
 
